@@ -19,6 +19,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -406,6 +407,51 @@ def pa_mean(metrics):
     return float(np.mean(np.concatenate(v))) if v else None
 
 
+DUMP_WEIGHT_SAMPLE = 16384         # elements of each sequence's weight arena (and Adam moments) in --dump-outputs
+DUMP_ARRAY_LIMIT = 1 << 20         # elements per dumped array: 12 arrays x 4 MB stay under the 64 MB a dump may take
+DUMP_SEED = 20240611
+
+
+def _dump_sample(a, seed):
+    """`a` as float32, or a fixed seeded sample of DUMP_ARRAY_LIMIT of its elements (flattened, in index order) when it is larger."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.size <= DUMP_ARRAY_LIMIT:
+        return a
+    idx = np.sort(np.random.default_rng(seed).choice(a.size, DUMP_ARRAY_LIMIT, replace=False))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(runner, metrics, out_dir):
+    """--dump-outputs: what the timed loop's last step handed its caller, one float32 .npy per array under out_dir, read after the clock
+    stopped and before any further step.  Per sequence (leading axis, in Runner order): the frame's errors from the metric flush
+    (mpjpe / pampjpe [S][B] in mm, pve [S]), the final inference of the native stepper (pred_rotmat [S][B][24][3][3], pred_shape,
+    pred_cam, pred_joints [S][B][49][3], pred_vertices [S][B][6890][3]) and the adapted weights with both Adam moments at a fixed seeded
+    sample of DUMP_WEIGHT_SAMPLE positions of the parameter arena (theta / adam_m / adam_v [S][DUMP_WEIGHT_SAMPLE]; the whole arenas are
+    ~100 MB per sequence).  The inputs are seeded, so two builds run with the same arguments can be compared file for file."""
+    ads = [runner.ad] if runner.grp is None else runner.ads
+    torch.cuda.synchronize()
+    arrays = dict(mpjpe=[m["mpjpe"][-1] for m in metrics], pampjpe=[m["pampjpe"][-1] for m in metrics], pve=[m["pve"][-1] for m in metrics])
+    # the stepper's output buffer holds a sequence's final inference unless a replica left the dynamic-BOA loop before the last launch
+    # (full term set, several sequences: dyb_stepper_output follows the last launch's arena) - those runs dump no predictions
+    if all(a._native is not None for a in ads) and not (ads[0]._native.full and len(ads) > 1):
+        outs = [[a._native.output(k, a._native_replica).cpu().numpy() for k in range(4)] for a in ads]
+        arrays.update(pred_rotmat=[o[0].reshape(-1, 24, 3, 3) for o in outs], pred_shape=[o[1][:, 144:154] for o in outs],
+                      pred_cam=[o[1][:, 154:157] for o in outs], pred_vertices=[o[2] for o in outs], pred_joints=[o[3] for o in outs])
+    thetas = [getattr(a.model, "module", a.model).theta for a in ads]
+    n = thetas[0].numel()
+    idx = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(n, DUMP_WEIGHT_SAMPLE), replace=False))).to(thetas[0].device)
+    arrays["theta"] = [t.detach()[idx].cpu().numpy() for t in thetas]
+    for name, key in (("adam_m", "exp_avg"), ("adam_v", "exp_avg_sq")):
+        arrays[name] = [a.optimizer.state[t][key][idx].cpu().numpy() for a, t in zip(ads, thetas)]
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, per_seq in sorted(arrays.items()):
+        a = _dump_sample(np.stack([np.asarray(x, np.float32) for x in per_seq]), DUMP_SEED + zlib.crc32(name.encode()))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, total
+
+
 def replica_run(device, S, steps, warmup, batch, inner_step, rank=0, **kw):
     """Aggregate frames/s of S sequences in lockstep on one GPU (a short side run: see Runner).  S = 1, the latency
     configuration, runs 200 frames and also reports the per-frame completion intervals."""
@@ -449,14 +495,11 @@ def sub_record(device, name, steps, warmup, batch, inner_step, note, roofline_pe
     one-sequence default-term-set run (two pass streams of its own, round 5) the later side runs lost 8 - 50 % in the same process and
     nothing as fresh processes (profiles/r05_sessions.txt s26 / s27).  DYB_BENCH_SUB_INPROC=1 keeps them in this process."""
     if os.environ.get("DYB_BENCH_SUB_INPROC") == "1":
-        kw.pop("env", None)
         return sub_record_here(device, name, steps, warmup, batch, inner_step, note, roofline_peak, seqs, **kw)
     import subprocess
-    child_env = dict(os.environ, **{k: str(v) for k, v in (kw.pop("env", None) or {}).items()})
     spec = dict(name=name, steps=steps, warmup=warmup, batch=batch, inner_step=inner_step, note=note, roofline_peak=roofline_peak, seqs=seqs, kw=kw)
     try:
-        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--sub_record", json.dumps(spec)], capture_output=True, text=True, timeout=900,
-                             env=child_env)
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--sub_record", json.dumps(spec)], capture_output=True, text=True, timeout=900)
         sys.stderr.write("".join(l + "\n" for l in out.stderr.splitlines() if l.startswith("[bench]")))
         line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
         return json.loads(line)
@@ -575,6 +618,9 @@ def main():
     ap.add_argument("--all_sub_records", action="store_true",
                     help="also the side runs whose kernels have not changed since round 3 (finite-difference HVP, batch 16 on the latency "
                          "schedule, the 32-sequence bf16 arm)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what their last step computed (predictions, errors, a sample of the adapted weights) "
+                         "as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline_worker(args.inner_step)))
@@ -665,6 +711,8 @@ def main():
             if args.probe_out:
                 json.dump(pr, open(args.probe_out, "w"), indent=1)
     dt, t_issue, metrics, run = res["dt"], res["t_issue"], res["metrics"], res["run"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(rn, metrics, args.dump_outputs)
     if dist is not None:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -868,20 +916,16 @@ def main():
                     device, "b16_fp32_lat", 10, 3, 16, args.inner_step, "configs[4] arm: batch 16, fp32, the latency schedule (64x64 kernel, "
                     "GroupNorm backward in the loaders) that batches below 8 use (switch tp_batch_min = 0)", roofline_peak=PEAK_FP32_MFMA_TFLOPS,
                     tp_batch_min=0)
-            Q8 = dict(GPU_MAX_HW_QUEUES="8")
-            q8_note = ("; GPU_MAX_HW_QUEUES=8 for this run: the chain, the weight-gradient stream and the two pass streams of a level then each have a "
-                       "hardware queue (78 frames/s with the runtime's default 4, 65 with the passes in sequence)")
             out["full_default_losses"] = sub_record(device, "full_default_losses", 24, 6, 1, 1,
                                                     "the reference's default flags (inner_step 1, teacher + motion + labelled exemplars + "
-                                                    "dynamic-BOA gate), ONE sequence - the configuration of the reference's published run" + q8_note,
-                                                    full_losses=1, env=Q8)
+                                                    "dynamic-BOA gate), ONE sequence - the configuration of the reference's published run",
+                                                    full_losses=1)
             torch.cuda.empty_cache()
             out["full_default_losses_S32"] = sub_record(
                 device, "full_default_losses_S32", 10, 3, 1, 1, "the reference's default flags (inner_step 1, teacher + motion + labelled "
                 "exemplars + dynamic-BOA gate decided per sequence) for 32 sequences in lockstep on this GPU: teacher forward, history-frame "
                 "pass and exemplar pass are replica-batched launches; a sequence whose gate has closed leaves the launch set of the "
-                "remaining extra steps; GPU_MAX_HW_QUEUES=8 (the level's passes run on streams of their own: +1 % here, +9 % at 5 sequences, s32)",
-                roofline_peak=PEAK_FP32_MFMA_TFLOPS, seqs=32, full_losses=1, env=Q8)
+                "remaining extra steps", roofline_peak=PEAK_FP32_MFMA_TFLOPS, seqs=32, full_losses=1)
             torch.cuda.empty_cache()
             # every default-term-set record above and below has each sequence's retrieval() upload its own exemplar copy from
             # (pinned) host memory inside the clock, as the reference does per level (base_adaptor.py:82-96).  This one is the round-5
@@ -889,19 +933,19 @@ def main():
             out["full_default_losses_S32_exemplars_resident"] = sub_record(
                 device, "full_default_losses_S32_exemplars_resident", 10, 3, 1, 1, "full_default_losses_S32 with EXEMPLARS RESIDENT: one generation + "
                 "one upload per step shared by all 32 sequences (synthetic exemplars depend on the step only) - NOT what the reference does; "
-                "round 5's 385 frames/s was measured this way", roofline_peak=None, seqs=32, full_losses=1, resident_exemplars=1, env=Q8)
+                "round 5's 385 frames/s was measured this way", roofline_peak=None, seqs=32, full_losses=1, resident_exemplars=1)
             torch.cuda.empty_cache()
             # the same two configurations with the dynamic loop actually ENTERED: threshold calibrated on this stream
             try:
                 thr, dtab = calibrate_gate_threshold(device)
                 note = ("the reference's default flags with cos_sim_threshold = %.3e (calibrated on this synthetic stream so that the dynamic-BOA "
                         "loop takes 2-3 extra upper-level steps per frame, as on real video; with the default 3.1e-4 it never opens here)" % thr)
-                out["full_default_losses_dynamic"] = sub_record(device, "full_default_losses_dynamic", 16, 4, 1, 1, note + q8_note, full_losses=1,
-                                                                cos_sim_threshold=thr, env=Q8)
+                out["full_default_losses_dynamic"] = sub_record(device, "full_default_losses_dynamic", 16, 4, 1, 1, note, full_losses=1,
+                                                                cos_sim_threshold=thr)
                 torch.cuda.empty_cache()
                 out["full_default_losses_dynamic_S32"] = sub_record(device, "full_default_losses_dynamic_S32", 8, 2, 1, 1, note + "; 32 sequences in "
-                                                                    "lockstep, the gate decided per sequence; GPU_MAX_HW_QUEUES=8 (+6.5 %, s32)", roofline_peak=None,
-                                                                    seqs=32, full_losses=1, cos_sim_threshold=thr, env=Q8)
+                                                                    "lockstep, the gate decided per sequence", roofline_peak=None,
+                                                                    seqs=32, full_losses=1, cos_sim_threshold=thr)
                 out["full_default_losses_dynamic"]["calibration"] = dtab
             except Exception as e:      # noqa: BLE001
                 out["full_default_losses_dynamic"] = dict(value=None, error=f"{type(e).__name__}: {e}")

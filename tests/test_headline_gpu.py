@@ -209,6 +209,38 @@ def test_bench_multi_rank_control_flow_on_one_gpu():
     assert op.get("value") and op["sequences_per_gpu"] == 19, op     # ceil(37 / 2)
 
 
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """`bench.py --dump-outputs DIR`: after exactly --steps timed steps (the record's `steps`, `ms_per_step` x steps = the timed window)
+    the last step's predictions, errors and weight / Adam-moment sample land in DIR as float32 .npy files of at most 64 MB in all, and
+    a second process with the same arguments writes the same arrays bit for bit (seeded inputs; the launch order is fixed)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    seqs, steps = 2, 3
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                              "--seqs", str(seqs), "--no_sub_records", "--no_cpu_baseline", "--no_roofline", "--percentile_frames", "0",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-3000:]
+        rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert rec["steps"] == steps
+        assert abs(rec["value"] - steps * seqs / (rec["ms_per_step"] * 1e-3 * steps)) < 1e-6 * rec["value"]
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["adam_m", "adam_v", "mpjpe", "pampjpe", "pred_cam", "pred_joints", "pred_rotmat", "pred_shape", "pred_vertices",
+                         "pve", "theta"], sorted(a)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["pred_vertices"].shape == (seqs, 1, 6890, 3) and a["theta"].shape[0] == seqs
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), k
+    assert np.abs(a["adam_m"]).max() > 0                          # the sample holds adapted state, not an untouched arena
+
+
 def test_fast_weights_from_the_weight_gradient_epilogue_are_bit_identical_to_the_streaming_pass(headline_switches, monkeypatch):
     """"fuse_fast" (round 6): on the throughput schedule a lower level's unsplit weight gradients write theta_next = theta_cur - fastlr * g
     from their accumulators (the levels ping-pong between two fast-weight buffers; the streaming pass covers the rest of the arena by
