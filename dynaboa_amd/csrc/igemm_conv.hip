@@ -1702,6 +1702,13 @@ static int run_igemm_tp(int mode, const ConvDesc& d, IgemmArgs g, float* out, co
   g.out = (split || g.compact) ? reinterpret_cast<float*>(ws) : out;          // (compact: always through the scatter fold)
   g.addend = (split || g.compact) ? nullptr : addend;
   g.out_scale = 1.f;
+  dim3 grid(mtiles, dyb_cdiv(g.Ncols, TN), g.nsplit * R.n);
+  g.probe = probe_for(mode, d, (long)grid.x * grid.y * grid.z);
+  // "tp_kernel" 2 (default): the software-pipelined loop (PIPE 1), 3: the same with two K-steps of loads in flight (PIPE 2);
+  // 1: round 2's phase-separated loop (also what the phase probe and
+  // weight gradients over maps too small for the branch-free pixel walk use)
+  const int tpk = switches().tp_kernel.load(std::memory_order_relaxed);
+  const int pipe = (tpk >= 2 && !g.probe && !(mode == MODE_WGRAD && TPK / g.Wo >= g.Ho)) ? (tpk >= 3 ? 2 : 1) : 0;
   // (a SPLIT weight gradient whose slabs the fold launch below adds: the fast-weight step rides in that launch - not Adam, not the in-kernel fold)
   const float* red_addend = addend;
   float* red_out = out;
@@ -1715,7 +1722,9 @@ static int run_igemm_tp(int mode, const ConvDesc& d, IgemmArgs g, float* out, co
       if (t_wupd.spans) t_wupd.spans->push_back(DybSpan{off, per});
     }
   }
-  if (mode == MODE_WGRAD && t_wupd.grads && !split && !g.compact && !addend) {
+  // (an UNSPLIT one: the epilogue writes the fast-weight step, or applies Adam - which only the pipelined loop forms carry: with pipe == 0
+  // an Adam scope is declined, the plain gradient goes to the gradient arena and the streaming Adam pass covers it, as no span is pushed)
+  if (mode == MODE_WGRAD && t_wupd.grads && !split && !g.compact && !addend && (!t_wupd.adam_m || pipe != 0)) {
     const char *lo = reinterpret_cast<const char*>(t_wupd.grads), *o = reinterpret_cast<const char*>(out);
     if (o >= lo && o + per * sizeof(float) <= lo + t_wupd.bytes) {
       const size_t off = (size_t)(o - lo) / sizeof(float);
@@ -1730,13 +1739,6 @@ static int run_igemm_tp(int mode, const ConvDesc& d, IgemmArgs g, float* out, co
       if (t_wupd.spans) t_wupd.spans->push_back(DybSpan{off, per});
     }
   }
-  dim3 grid(mtiles, dyb_cdiv(g.Ncols, TN), g.nsplit * R.n);
-  g.probe = probe_for(mode, d, (long)grid.x * grid.y * grid.z);
-  // "tp_kernel" 2 (default): the software-pipelined loop (PIPE 1), 3: the same with two K-steps of loads in flight (PIPE 2);
-  // 1: round 2's phase-separated loop (also what the phase probe and
-  // weight gradients over maps too small for the branch-free pixel walk use)
-  const int tpk = switches().tp_kernel.load(std::memory_order_relaxed);
-  const int pipe = (tpk >= 2 && !g.probe && !(mode == MODE_WGRAD && TPK / g.Wo >= g.Ho)) ? (tpk >= 3 ? 2 : 1) : 0;
   // in-kernel fold ("tp_fold"): a counter region in scope, the pipelined kernel, plain slabs (not the compact stride-2 form)
   const bool fold = split && !g.compact && pipe != 0 && t_conv_sync.ctr && (long)grid.x * grid.y * R.n <= (long)t_conv_sync.nwords &&
                     !(raw_slabs_out && mode != MODE_FWD) && ((switches().tp_fold.load(std::memory_order_relaxed) >> mode) & 1);   // bit per mode
@@ -1753,7 +1755,7 @@ static int run_igemm_tp(int mode, const ConvDesc& d, IgemmArgs g, float* out, co
   }
   const bool bf = dyb_bf16_current();
   DYB_REQUIRE(!bf || pipe != 0, DYB_ERR_UNSUPPORTED);
-  DYB_REQUIRE(!g.adam_m || pipe != 0, DYB_ERR_UNSUPPORTED);        // (the Adam epilogue lives in the pipelined forms)
+  DYB_REQUIRE(!g.adam_m || pipe != 0, DYB_ERR_UNSUPPORTED);        // (the Adam epilogue lives in the pipelined forms; a scope is declined above)
   GnFwdFuse nf{};
   if (nfuse) nf = *nfuse;
   DYB_REQUIRE(!nfuse || d.N <= 64, DYB_ERR_UNSUPPORTED);

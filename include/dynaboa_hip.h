@@ -346,8 +346,9 @@ int dyb_sync_error_count(unsigned* count_host, dyb_stream_t stream);
  * conv calls, until reset with (NULL, 0).  With a region in scope a split launch's last-arriving workgroup per tile adds the slabs
  * itself (csrc/igemm_tp.inc); the engine passes its own regions per pass.  Option "stat_folds" counts such launches. */
 int dyb_debug_set_conv_sync(unsigned* ctr, int nwords);
-/* tests / lab ("fuse_fast", round 6): while set, a throughput-form weight gradient of the calling thread that runs UNSPLIT and whose
- * result would land inside [grads, grads + bytes) writes p_next[off] = p_cur[off] - lr * g from its accumulators instead of g - the MAML
+/* tests / lab ("fuse_fast", round 6): while set, a weight gradient of the calling thread whose result would land inside [grads, grads + bytes)
+ * writes p_next[off] = p_cur[off] - lr * g instead of g - from its accumulators when it runs unsplit, from the fold launch that adds its
+ * slabs when it splits (not with the throughput kernel's in-kernel fold), in the latency form's fp32 kernel too - the MAML
  * fast-weight step (learn2learn MAML.adapt: p' = p - lr * dL/dp; reference dynaboa_benchmark.py:136,140) fused into the convolution's
  * epilogue.  Reset with grads = NULL.  dyb_debug_wgrad_update_spans: how many launches took that form since the scope was set.  The frame
  * stepper opens such a scope around every lower level's backward (csrc/adapt_step.hip). */
@@ -356,7 +357,9 @@ int dyb_debug_wgrad_update_spans(void);
 /* the same for Adam ("fuse_adam"): an unsplit throughput-form weight gradient whose result would land inside [grads, grads + bytes) applies
  * torch.optim.Adam's single-tensor step (reference base_adaptor.py:126, dynaboa_benchmark.py:149-151) to theta / m / v IN PLACE at the same
  * offset from its accumulators; sc = device pointer to (step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t)).  Reset with
- * dyb_debug_set_wgrad_update(NULL, ...).  The frame stepper opens such a scope around the outer level's backward of a replica group. */
+ * dyb_debug_set_wgrad_update(NULL, ...).  Only the pipelined loop forms carry that epilogue: with tp_kernel 1, a phase probe armed or a map
+ * too small for the pipelined pixel walk the scope is declined - the plain gradient is written, no span counted.  The frame stepper opens
+ * such a scope around the outer level's backward of a replica group. */
 int dyb_debug_set_wgrad_adam(const float* grads, size_t bytes, float* theta, float* m, float* v, const float* sc, float beta1, float beta2,
                              float eps);
 int dyb_set_option(const char* name, int value);

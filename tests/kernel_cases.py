@@ -73,87 +73,286 @@ def _conv_check(be, N, H, W, C, K, R, stride, pad, x, w, dy, add, xr, wr, dyr):
     return e
 
 
-def case_conv_wgrad_update(be, N, H, W, C, K, R, stride, pad, lr=0.37, seed=0):
-    """"fuse_fast" (round 6): with a weight-update scope set, an UNSPLIT throughput-form weight gradient leaves p_cur - lr * g in p_next
-    instead of g in dw (igemm_tp.inc epilogue: addend + out_scale * acc).  Against torch's gradient; dw must stay untouched.  The caller
-    has put the library on the throughput schedule with tp_grid small enough for nsplit == 1.  -> launches that took the fused form."""
-    rng = _rng(seed)
-    Ho, Wo = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
-    x = rng.standard_normal((N, H, W, C)).astype(np.float32)
-    dy = rng.standard_normal((N, Ho, Wo, K)).astype(np.float32)
-    p_cur = rng.standard_normal((R, R, C, K)).astype(np.float32)
-    xt = torch.from_numpy(x).permute(0, 3, 1, 2).contiguous()
-    wt = torch.zeros(K, C, R, R, requires_grad=True)
-    (gw,) = torch.autograd.grad(F.conv2d(xt, wt, stride=stride, padding=pad), [wt], torch.from_numpy(dy).permute(0, 3, 1, 2))
-    dw_ref = gw.permute(2, 3, 1, 0).numpy()
-    wsb = be.lib.dyb_conv2d_workspace_bytes(N, H, W, C, K, R, R, stride, pad)
-    ws = be.empty((max(wsb, 16) // 4,))
-    marker = np.full(p_cur.shape, 7.25, np.float32)
-    X, DY, P0 = be.dev(x), be.dev(dy), be.dev(p_cur)
-    dw_, p1_ = be.dev(marker), be.dev(np.zeros_like(p_cur))
-    check(be.lib.dyb_debug_set_wgrad_update(be.ptr(dw_), p_cur.size * 4, be.ptr(P0), be.ptr(p1_), lr), "set_wgrad_update")
+# ---------------------------------------------------------------------------------------- fused weight updates
+# "fuse_fast" / "fuse_adam" (round 6): under a weight-update scope (DybWgradUpdateScope; dyb_debug_set_wgrad_update / _adam for
+# direct calls) a weight gradient whose output lies inside the scope's gradient range does not write the gradient: it writes
+# p_next = p_cur - lr * g, or applies Adam to (theta, exp_avg, exp_avg_sq) in place, at the same offset of the scope's weight arenas.
+# The cases below put the layer's tensor at ARENA_HEAD floats into a range of ARENA_HEAD + n + ARENA_TAIL, every float around it a
+# marker; each run checks (a) the plain gradient g_k of the same launch without a scope against a float64 torch gradient, (b) the fused
+# result against the streaming kernel (dyb_fastweight_update / dyb_adam_step) on g_k, bit for bit, (c) the fused result against a float64
+# restatement of the update on g_k - and which form the launch took.
+ARENA_HEAD, ARENA_TAIL = 300, 164        # multiples of 4, like the offsets of the arena's tensors
+
+# Adam settings: t = 1 from zero moments; a later step with moments of the gradient's size; a later step where eps dominates the
+# denominator (gradient and moments ~1e-11: sqrt(v) / bc2_sqrt ~1e-11 << eps).  lr sized so a step is >> one ulp of theta ~ N(0, 1).
+ADAM_REGIMES = {
+    "t1": dict(t=1, b1=0.5, b2=0.9, lr=1e-2, dy=0.1, moments=False),          # beta1 = 0.5: the reference's default
+    "t10": dict(t=10, b1=0.9, b2=0.999, lr=1e-2, dy=0.1, moments=True),
+    "eps": dict(t=10, b1=0.5, b2=0.9, lr=1.0, dy=1e-11, moments=True),
+}
+ADAM_EPS = 1e-8
+FAST_LR = 0.37
+
+
+def _arena(rng, n, inner=None):
+    """host float32 arena of ARENA_HEAD + n + ARENA_TAIL random markers; `inner` (n floats) at ARENA_HEAD"""
+    a = (rng.standard_normal(ARENA_HEAD + n + ARENA_TAIL) * 3.0 + 11.0).astype(np.float32)
+    if inner is not None:
+        a[ARENA_HEAD:ARENA_HEAD + n] = np.asarray(inner, np.float32).ravel()
+    return a
+
+
+def _with_span(arena, n, inner):
+    e = arena.copy()
+    e[ARENA_HEAD:ARENA_HEAD + n] = np.asarray(inner, np.float32).ravel()
+    return e
+
+
+def _assert_arena(name, got, expect, n):
+    """bit for bit: the floats around the tensor's span, then the span"""
+    got, expect = np.asarray(got).view(np.uint32), np.asarray(expect).view(np.uint32)
+    h, t = slice(0, ARENA_HEAD), slice(ARENA_HEAD + n, None)
+    bad = int((got[h] != expect[h]).sum() + (got[t] != expect[t]).sum())
+    assert bad == 0, f"{name}: {bad} floats outside the tensor's span changed"
+    s = slice(ARENA_HEAD, ARENA_HEAD + n)
+    bad = int((got[s] != expect[s]).sum())
+    assert bad == 0, f"{name}: {bad} of {n} floats of the span differ from the streaming kernel on the plain gradient"
+
+
+def _scope_bytes(n, short):
+    """the scope's range; `short`: one float too short to contain the tensor (must not fuse)"""
+    return 4 * (ARENA_HEAD + n - 1 if short else ARENA_HEAD + n + ARENA_TAIL)
+
+
+def _check_fast_semantics(p_cur, p_next, g, lr):
+    """(c) p_next - p_cur against -lr * g in float64: one rounding of the fused multiply-add (<= 1/2 ulp of p_next)"""
+    p_cur, p_next, g = (np.asarray(a, np.float64).ravel() for a in (p_cur, p_next, g))
+    d_ref = -np.float64(np.float32(lr)) * g
+    err = np.abs((p_next - p_cur) - d_ref)
+    bound = np.spacing(np.abs(p_next).astype(np.float32)).astype(np.float64)
+    assert (err <= bound).all(), f"fast-weight step: {int((err > bound).sum())} elements off by more than one ulp"
+    assert np.median(np.abs(d_ref)) > 1e3 * np.median(bound), "lr too small for the check to see the step"
+    return float((err / bound).max())                       # (the share of the bound used)
+
+
+def adam_reference64(theta0, m0, v0, g, t, lr, b1, b2, eps):
+    """torch.optim.Adam's single-tensor step (foreach=False, amsgrad off, no weight decay) restated in float64:
+    m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  theta -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+    -> (delta of theta, m, v, step_size, bc2_sqrt)"""
+    theta0, m0, v0, g = (np.asarray(a, np.float64).ravel() for a in (theta0, m0, v0, g))
+    m = b1 * m0 + (1.0 - b1) * g
+    v = b2 * v0 + (1.0 - b2) * g * g
+    ss, bc = lr / (1.0 - b1 ** t), np.sqrt(1.0 - b2 ** t)
+    return -ss * m / (np.sqrt(v) / bc + eps), m, v, ss, bc
+
+
+def _check_adam_semantics(theta0, m0, v0, g, theta1, m1, v1, rg):
+    """(c) the fused Adam results against adam_reference64 on the same gradient: moments to 1e-6 of their terms, the theta step within
+    two ulp of theta plus 1e-5 of the step (plus what the moment's own rounding carries into it)"""
+    # (the betas as the float32 values the ABI takes: 1 - b2 of float32(0.999) is 1.3e-5 away from 0.001)
+    t, lr, b1, b2 = rg["t"], rg["lr"], float(np.float32(rg["b1"])), float(np.float32(rg["b2"]))
+    d_ref, m_ref, v_ref, ss, bc = adam_reference64(theta0, m0, v0, g, t, lr, b1, b2, ADAM_EPS)
+    theta0, m0, g, theta1, m1, v1 = (np.asarray(a, np.float64).ravel() for a in (theta0, m0, g, theta1, m1, v1))
+    m_terms = b1 * np.abs(m0) + (1.0 - b1) * np.abs(g)
+    e = dict(m=float((np.abs(m1 - m_ref) / np.maximum(m_terms, 1e-300)).max()),
+             v=float((np.abs(v1 - v_ref) / np.maximum(v_ref, 1e-300)).max()))
+    assert (np.abs(m1 - m_ref) <= 1e-6 * m_terms).all(), ("exp_avg", e)
+    assert (np.abs(v1 - v_ref) <= 1e-6 * v_ref).all(), ("exp_avg_sq", e)
+    denom = np.sqrt(v_ref) / bc + ADAM_EPS
+    ulp = np.spacing(np.maximum(np.abs(theta0), np.abs(theta1)).astype(np.float32)).astype(np.float64)
+    bound = 2.0 * ulp + 1e-5 * np.abs(d_ref) + ss * 1e-6 * m_terms / denom
+    err = np.abs((theta1 - theta0) - d_ref)
+    e["theta"] = float((err / bound).max())                 # (the share of the bound used)
+    assert (err <= bound).all(), (f"theta step: {int((err > bound).sum())} of {err.size} elements out of bounds", e)
+    assert np.median(np.abs(d_ref)) > 1e3 * np.median(ulp), "lr too small for the check to see the step"
+    if rg["dy"] < 1e-6:
+        assert np.mean(np.sqrt(v_ref) / bc < 0.2 * ADAM_EPS) > 0.9, "eps regime: eps does not dominate the denominator"
+    return e
+
+
+def _adam_state(rng, g, rg):
+    """(theta0, m0, v0) for one Adam regime, moments scaled to the gradient"""
+    n = g.size
+    theta0 = rng.standard_normal(n).astype(np.float32)
+    if not rg["moments"]:
+        return theta0, np.zeros(n, np.float32), np.zeros(n, np.float32)
+    s = float(np.std(np.asarray(g, np.float64))) or 1.0
+    m0 = (rng.standard_normal(n) * s).astype(np.float32)
+    v0 = (rng.uniform(0.1, 2.0, n) * s * s).astype(np.float32)
+    return theta0, m0, v0
+
+
+def _fused_update(be, update, g_k, n, launch, expect_fused, seed, short=False, regime="t10"):
+    """The scope part shared by the conv and linear cases: runs launch(ptr into the gradient arena) under a fast-weight (update "fast")
+    or Adam ("adam", ADAM_REGIMES[regime]) scope over arenas with the tensor at ARENA_HEAD; checks the form against `expect_fused`, (b),
+    (c) and the weight arenas' markers.  -> (errors of (c), host gradient arena after the launch, its markers)"""
+    rng = _rng(seed + 1000)
+    g_k = np.asarray(g_k, np.float32).ravel()
+    G0 = _arena(rng, n)
+    G = be.dev(G0)
+    at = lambda b: be.ptr(b) + 4 * ARENA_HEAD
+    nbytes = _scope_bytes(n, short)
+    GK = be.dev(g_k)
+    if update == "fast":
+        p_cur = (rng.standard_normal(n)).astype(np.float32)
+        P00, P10 = _arena(rng, n, p_cur), _arena(rng, n)
+        P0, P1 = be.dev(P00), be.dev(P10)
+        check(be.lib.dyb_debug_set_wgrad_update(be.ptr(G), nbytes, be.ptr(P0), be.ptr(P1), FAST_LR), "set_wgrad_update")
+    else:
+        rg = ADAM_REGIMES[regime]
+        theta0, m0, v0 = _adam_state(rng, g_k, rg)
+        T0, M0, V0 = _arena(rng, n, theta0), _arena(rng, n, m0), np.abs(_arena(rng, n, v0))
+        TH, M, V = be.dev(T0), be.dev(M0), be.dev(V0)
+        t, b1, b2 = rg["t"], rg["b1"], rg["b2"]
+        sc = np.array([rg["lr"] / (1.0 - b1 ** t), np.sqrt(1.0 - b2 ** t)], np.float32)      # as the stepper computes them
+        SC = be.dev(sc)
+        check(be.lib.dyb_debug_set_wgrad_adam(be.ptr(G), nbytes, be.ptr(TH), be.ptr(M), be.ptr(V), be.ptr(SC), b1, b2, ADAM_EPS),
+              "set_wgrad_adam")
     try:
-        check(be.lib.dyb_conv2d_nhwc_wgrad(be.ptr(X), be.ptr(DY), be.ptr(dw_), N, H, W, C, K, R, R, stride, pad, be.ptr(ws), wsb, be.stream),
-              "conv wgrad (update scope)")
+        launch(at(G))
         be.sync()
         fused = int(be.lib.dyb_debug_wgrad_update_spans())
     finally:
         be.lib.dyb_debug_set_wgrad_update(None, 0, None, None, 0.0)
-    if fused:
-        assert np.array_equal(be.host(dw_), marker), "the gradient buffer was written although the update was fused"
-        e = rel_err(be.host(p1_), p_cur - np.float32(lr) * dw_ref)
+    assert fused == int(expect_fused), f"{update}: {fused} launches took the fused form, expected {int(expect_fused)}"
+    e = {}
+    if update == "fast":
+        _assert_arena("p_cur", be.host(P0), P00, n)
+        if fused:
+            FW = be.empty((n,))
+            check(be.lib.dyb_fastweight_update(at(P0), be.ptr(GK), be.ptr(FW), FAST_LR, n, be.stream), "fastweight")
+            _assert_arena("p_next", be.host(P1), _with_span(P10, n, be.host(FW)), n)
+            e["fast"] = _check_fast_semantics(p_cur, be.host(P1)[ARENA_HEAD:ARENA_HEAD + n], g_k, FAST_LR)
+        else:
+            _assert_arena("p_next (not fused: untouched)", be.host(P1), P10, n)
     else:
-        e = rel_err(be.host(dw_), dw_ref)
-    assert e < TOL, e
-    return fused
+        if fused:
+            TS, MS, VS = be.dev(theta0), be.dev(m0), be.dev(v0)
+            check(be.lib.dyb_adam_step(be.ptr(TS), be.ptr(GK), be.ptr(MS), be.ptr(VS), b1, b2, float(sc[0]), float(sc[1]), ADAM_EPS, n,
+                                       be.stream), "adam")
+            th1, m1, v1 = be.host(TS), be.host(MS), be.host(VS)
+            _assert_arena("theta", be.host(TH), _with_span(T0, n, th1), n)
+            _assert_arena("exp_avg", be.host(M), _with_span(M0, n, m1), n)
+            _assert_arena("exp_avg_sq", be.host(V), _with_span(V0, n, v1), n)
+            e.update(_check_adam_semantics(theta0, m0, v0, g_k, th1, m1, v1, rg))
+        else:
+            for name, b, ref in (("theta", TH, T0), ("exp_avg", M, M0), ("exp_avg_sq", V, V0)):
+                _assert_arena(name + " (not fused: untouched)", be.host(b), ref, n)
+    return e, be.host(G), G0
 
 
-def case_conv_wgrad_adam(be, N, H, W, C, K, R, stride, pad, seed=0, t_step=3):
-    """"fuse_adam" (round 6): with an Adam scope set, an UNSPLIT throughput-form weight gradient applies torch.optim.Adam's step to theta /
-    exp_avg / exp_avg_sq in place from its accumulators (igemm_tp.inc).  Against torch.optim.Adam itself on torch's gradient (step
-    t_step: bias corrections as the stepper computes them); the gradient buffer must stay untouched.  -> launches that took the form."""
+def conv_launch_form(be, run):
+    """(kind, nsplit) of the one conv launch run() makes, from a timing scope's per-shape table: kind v = the throughput kernel's weight
+    gradient, w = the latency form's"""
+    import ctypes
+    check(be.lib.dyb_conv_timing_begin(8), "timing_begin")
+    try:
+        run()
+        be.sync()
+    finally:
+        ms, cnt, fl, by = ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double(), ctypes.c_double()
+        check(be.lib.dyb_conv_timing_end(ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(fl), ctypes.byref(by)), "timing_end")
+    need = be.lib.dyb_conv_timing_table(None, 0)
+    buf = ctypes.create_string_buffer(int(need))
+    be.lib.dyb_conv_timing_table(buf, need)
+    rows = buf.value.decode().strip().splitlines()[1:]
+    assert cnt.value == 1 and len(rows) == 1, rows
+    f = rows[0].split(",")
+    return f[0], int(f[9])
+
+
+def case_conv_wgrad_fused(be, N, H, W, C, K, R, stride, pad, update, expect_fused, seed=0, regime="t10", c_real=None, bf16=False,
+                          short=False):
+    """A weight gradient of conv(x, w) under a fast-weight (update="fast") or Adam ("adam", ADAM_REGIMES[regime]) scope, with the
+    library's current options (the caller picks schedule, loop form, split): (a) the plain gradient g_k of the same launch without a
+    scope against a float64 torch gradient; the scoped launch must take the form `expect_fused` says (a bool, or a rule: a function of
+    the plain launch's (kind, nsplit) - e.g. "Adam fuses where the launch is unsplit" at a split policy's default) - fused: the gradient arena keeps
+    its markers, the span holds the streaming kernel's result on g_k bit for bit and (c) matches the float64 restatement; not fused: g_k
+    lands in the gradient arena bit for bit, the weight arenas stay untouched.  Nothing outside the span moves.
+    bf16=True: the option "bf16" on for both launches; (a) against the convolution of the bf16-rounded operands.
+    c_real: input channels >= c_real are zero (the stem's padding channel): their gradient rows must be exact zeros.
+    -> dict(form=(kind, nsplit) of the plain launch, err=errors)"""
     rng = _rng(seed)
     Ho, Wo = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
     x = rng.standard_normal((N, H, W, C)).astype(np.float32)
-    dy = (rng.standard_normal((N, Ho, Wo, K)) * 0.1).astype(np.float32)
-    theta = rng.standard_normal((R, R, C, K)).astype(np.float32)
-    m0 = (rng.standard_normal(theta.shape) * 0.05).astype(np.float32)
-    v0 = (rng.random(theta.shape) * 0.01).astype(np.float32)
-    lr, b1, b2, eps = 3e-3, 0.5, 0.9, 1e-8
-    xt = torch.from_numpy(x).permute(0, 3, 1, 2).contiguous()
-    wt = torch.zeros(K, C, R, R, requires_grad=True)
-    (gw,) = torch.autograd.grad(F.conv2d(xt, wt, stride=stride, padding=pad), [wt], torch.from_numpy(dy).permute(0, 3, 1, 2))
-    g = gw.permute(2, 3, 1, 0).contiguous()
-    # torch.optim.Adam at step t_step with these moments (single-tensor formula)
-    p = torch.nn.Parameter(torch.from_numpy(theta.copy()))
-    opt = torch.optim.Adam([p], lr=lr, betas=(b1, b2), eps=eps, foreach=False)
-    opt.state[p] = dict(step=torch.tensor(float(t_step - 1)), exp_avg=torch.from_numpy(m0.copy()), exp_avg_sq=torch.from_numpy(v0.copy()))
-    p.grad = g.clone()
-    opt.step()
-    sc = np.array([lr / (1.0 - b1 ** t_step), np.sqrt(1.0 - b2 ** t_step)], np.float32)
+    if c_real is not None:
+        x[..., c_real:] = 0
+    # (Adam: dy scaled so the gradient is ~ADAM_REGIMES[regime]["dy"] whatever the reduction length)
+    scale = ADAM_REGIMES[regime]["dy"] / np.sqrt(N * Ho * Wo) if update == "adam" else 1.0
+    dy = (rng.standard_normal((N, Ho, Wo, K)) * scale).astype(np.float32)
+    xr, dyr = (bf16_round(x), bf16_round(dy)) if bf16 else (x, dy)
+    xt = torch.from_numpy(xr).double().permute(0, 3, 1, 2).contiguous()
+    wt = torch.zeros(K, C, R, R, dtype=torch.float64, requires_grad=True)
+    (gw,) = torch.autograd.grad(F.conv2d(xt, wt, stride=stride, padding=pad), [wt], torch.from_numpy(dyr).double().permute(0, 3, 1, 2))
+    g_ref = gw.permute(2, 3, 1, 0).numpy()
+    n = R * R * C * K
     wsb = be.lib.dyb_conv2d_workspace_bytes(N, H, W, C, K, R, R, stride, pad)
     ws = be.empty((max(wsb, 16) // 4,))
-    marker = np.full(theta.shape, 7.25, np.float32)
-    X, DY, TH, M, V, SC = be.dev(x), be.dev(dy), be.dev(theta), be.dev(m0), be.dev(v0), be.dev(sc)
-    dw_ = be.dev(marker)
-    check(be.lib.dyb_debug_set_wgrad_adam(be.ptr(dw_), theta.size * 4, be.ptr(TH), be.ptr(M), be.ptr(V), be.ptr(SC), b1, b2, eps), "set_wgrad_adam")
+    X, DY = be.dev(x), be.dev(dy)
+
+    def launch(dw_ptr):
+        check(be.lib.dyb_conv2d_nhwc_wgrad(be.ptr(X), be.ptr(DY), dw_ptr, N, H, W, C, K, R, R, stride, pad, be.ptr(ws), wsb, be.stream),
+              "conv wgrad")
+    if bf16:
+        be.lib.dyb_set_option(b"bf16", 1)
     try:
-        check(be.lib.dyb_conv2d_nhwc_wgrad(be.ptr(X), be.ptr(DY), be.ptr(dw_), N, H, W, C, K, R, R, stride, pad, be.ptr(ws), wsb, be.stream),
-              "conv wgrad (Adam scope)")
-        be.sync()
-        fused = int(be.lib.dyb_debug_wgrad_update_spans())
+        GK = be.empty((n,))
+        form = conv_launch_form(be, lambda: launch(be.ptr(GK)))
+        g_k = be.host(GK)
+        e = dict(grad=rel_err(g_k.reshape(g_ref.shape), g_ref))
+        assert e["grad"] < TOL, e
+        if c_real is not None:
+            assert not g_k.reshape(R, R, C, K)[:, :, c_real:].any(), "gradient rows of zero input channels are not exact zeros"
+        if callable(expect_fused):
+            expect_fused = bool(expect_fused(form))
+        eu, Gh, G0 = _fused_update(be, update, g_k, n, launch, expect_fused, seed, short=short, regime=regime)
     finally:
-        be.lib.dyb_debug_set_wgrad_update(None, 0, None, None, 0.0)
-    if fused:
-        assert np.array_equal(be.host(dw_), marker), "the gradient buffer was written although Adam was fused"
-        st = opt.state[p]
-        e = dict(theta=rel_err(be.host(TH) - theta, p.detach().numpy() - theta), m=rel_err(be.host(M), st["exp_avg"].numpy()),
-                 v=rel_err(be.host(V), st["exp_avg_sq"].numpy()))
-        assert max(e.values()) < 5 * TOL, e
-    else:
-        assert rel_err(be.host(dw_), g.numpy()) < TOL
-        assert np.array_equal(be.host(TH), theta)
-    return fused
+        if bf16:
+            be.lib.dyb_set_option(b"bf16", 0)
+    _assert_arena("gradient arena", Gh, G0 if expect_fused else _with_span(G0, n, g_k), n)
+    e.update(eu)
+    return dict(form=form, err=e)
+
+
+def case_linear_wgrad_fused(be, B, I, O, T, update, expect_fused, ldw=None, seed=0, regime="t10"):
+    """dyb_linear_bwd_dw (linear_outer_kernel: dw = sum_t dy_t^T x_t over T terms of B rows, db = sum of dy rows) under a fast-weight or
+    Adam scope, as case_conv_wgrad_fused: (a) g_k and db of the plain launch against float64; the fused form (kind 1 / 2) when I == ldw,
+    the plain gradient (rows of ldw floats, the pad columns untouched) otherwise; db written plainly either way, bit for bit."""
+    import ctypes
+    ldw = ldw or I
+    rng = _rng(seed)
+    scale = ADAM_REGIMES[regime]["dy"] / np.sqrt(T * B) if update == "adam" else 1.0
+    dys = [(rng.standard_normal((B, O)) * scale).astype(np.float32) for _ in range(T)]
+    xs = [rng.standard_normal((B, I)).astype(np.float32) for _ in range(T)]
+    g_ref = sum(a.astype(np.float64).T @ b.astype(np.float64) for a, b in zip(dys, xs))
+    db_ref = sum(a.astype(np.float64).sum(0) for a in dys)
+    dyb, xb = [be.dev(a) for a in dys], [be.dev(a) for a in xs]
+    ka, pa = be.ptr_array(dyb)
+    kb, pb = be.ptr_array(xb)
+    ld1 = (ctypes.c_int * T)(*([O] * T))
+    ld2 = (ctypes.c_int * T)(*([I] * T))
+    n = O * ldw
+
+    def launch(dw_ptr, db):
+        check(be.lib.dyb_linear_bwd_dw(pa, ctypes.cast(ld1, ctypes.c_void_p), pb, ctypes.cast(ld2, ctypes.c_void_p), T, B, I, O, dw_ptr,
+                                       ldw, be.ptr(db), be.stream), "linear dw")
+    GK0 = (rng.standard_normal(n) + 5.0).astype(np.float32)
+    GK, DBK = be.dev(GK0), be.empty((O,))
+    launch(be.ptr(GK), DBK)
+    gk_full, db_k = be.host(GK), be.host(DBK)
+    pad_cols = np.zeros((O, ldw), bool)
+    pad_cols[:, I:] = True
+    assert np.array_equal(gk_full[pad_cols.ravel()], GK0[pad_cols.ravel()]), "the pad columns of dw were written"
+    g_k = gk_full.reshape(O, ldw)[:, :I]
+    e = dict(grad=rel_err(g_k, g_ref), db=rel_err(db_k, db_ref))
+    assert max(e.values()) < TOL, e
+    DB = be.empty((O,))
+    eu, Gh, G0 = _fused_update(be, update, gk_full, n, lambda p: launch(p, DB), expect_fused, seed, regime=regime)
+    assert np.array_equal(be.host(DB).view(np.uint32), db_k.view(np.uint32)), "bias gradient differs from the plain launch's"
+    _assert_arena("gradient arena", Gh, G0 if expect_fused else _with_span(G0, n, np.where(pad_cols.ravel(), G0[ARENA_HEAD:ARENA_HEAD + n],
+                                                                                          gk_full)), n)
+    e.update(eu)
+    return e
 
 
 def case_conv_inkernel_fold(be, N, H, W, C, K, R, stride, pad, seed=0):

@@ -272,6 +272,39 @@ def test_fast_weights_from_the_weight_gradient_epilogue_are_bit_identical_to_the
             assert torch.equal(a, b), float((a.double() - b.double()).norm() / b.double().norm())
 
 
+@pytest.mark.parametrize("tp_kernel", [1, 3], ids=["phased", "pipelined2"])
+def test_fused_weight_updates_with_the_other_loop_forms_are_bit_identical_to_the_streaming_passes(headline_switches, monkeypatch, tp_kernel):
+    """"fuse_fast" + "fuse_adam" against neither (DYB_FUSE_FAST/ADAM = 1/1 vs 0/0) with the throughput kernel's other loop forms:
+    tp_kernel 1 (phased loop - fast weights from its epilogue, Adam scopes declined: those gradients go to the streaming Adam pass) and
+    3 (pipelined, two K-steps in flight).  S = 8, two frames of 3 inner + 1 outer step: weights, Adam moments and metrics bit for bit."""
+    from dynaboa_amd import native_step as NS
+    lib = headline_switches
+    S, NF = 8, 2
+    frames = _frames(S, NF)
+    lib.dyb_set_option(b"tp_kernel", tp_kernel)
+    try:
+        assert _throughput_schedule_is_on(lib, S) and _opt(lib, b"tp_kernel") == tp_kernel
+        outs = []
+        for fuse in ("1", "0"):
+            monkeypatch.setenv("DYB_FUSE_FAST", fuse)
+            monkeypatch.setenv("DYB_FUSE_ADAM", fuse)
+            ads = [_mk(r) for r in range(S)]
+            grp = NS.ReplicaGroup(ads, NF)
+            for step in range(NF):
+                grp.step([frames[r][step] for r in range(S)], step)
+            fl = grp.flush_metrics()
+            st = [a.optimizer.state[a.model.module.theta] for a in ads]
+            outs.append([torch.stack([a.model.module.theta.detach() for a in ads]), torch.stack([s_["exp_avg"] for s_ in st]),
+                         torch.stack([s_["exp_avg_sq"] for s_ in st]),
+                         torch.tensor(np.array([np.ravel(np.array(fl[r]["mpjpe"], np.float64)) for r in range(S)]))])
+            del grp, ads
+    finally:
+        lib.dyb_set_option(b"tp_kernel", 2)
+    for a, b in zip(*outs):
+        assert torch.equal(a, b), float((a.double() - b.double()).norm() / b.double().norm())
+    assert outs[0][1].abs().max() > 0                                # Adam has run: the moments hold state
+
+
 def test_fast_weights_from_the_weight_gradient_epilogue_one_sequence(monkeypatch):
     """"fuse_fast" on the latency schedule (ONE sequence, the literal bs=1 stream): every lower-level weight gradient - unsplit, folded
     in-kernel or by the fold launch - and the regressor's matrices write the fast weights themselves; against the streaming pass over the

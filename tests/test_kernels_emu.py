@@ -517,26 +517,27 @@ def test_hmr_exact_hessian_vector_product_one_launch_groupnorm_tangents(be, ckpt
         be.lib.dyb_set_option(b"conv_pair", 1)
 
 
-@pytest.mark.parametrize("cfg", [
-    (1, 7, 7, 128, 256, 3, 1, 1),      # 49-pixel reduction (ragged last K-step), 128x128 tiles
-    (1, 12, 12, 128, 128, 1, 1, 0),    # 1x1
-    (2, 10, 10, 64, 64, 3, 2, 1),      # Cout = 64: the 256x64 form, stride 2, batch 2
-    (1, 14, 14, 64, 128, 1, 2, 0),     # 1x1 stride 2 (downsample)
-])
-def test_conv_weight_gradient_writes_fast_weights(be, cfg):
-    """"fuse_fast": the throughput-form weight gradient with a weight-update scope in force (kernel_cases.case_conv_wgrad_update) -
-    unsplit (tp_grid 1): p_next = p_cur - lr * g from the epilogue, the gradient buffer untouched; split (tp_grid 4096 where the shape
-    allows a split): the scope is ignored and the plain gradient arrives."""
+@pytest.mark.parametrize("cfg,splits", [
+    ((1, 7, 7, 128, 256, 3, 1, 1), False),      # 49-pixel reduction (ragged last K-step), 128x128 tiles: too short to split
+    ((1, 12, 12, 128, 128, 1, 1, 0), True),     # 1x1, 144 pixels: split in two at tp_grid 4096
+    ((2, 10, 10, 64, 64, 3, 2, 1), False),      # Cout = 64: the 256x64 form, stride 2, batch 2
+    ((1, 14, 14, 64, 128, 1, 2, 0), False),     # 1x1 stride 2 (downsample)
+], ids=["cfg0", "cfg1", "cfg2", "cfg3"])
+def test_conv_weight_gradient_writes_fast_weights(be, cfg, splits):
+    """"fuse_fast" / "fuse_adam": the throughput-form weight gradient (default loop form) with a weight-update scope in force
+    (kernel_cases.case_conv_wgrad_fused) - unsplit (tp_grid 1): both fused in the epilogue; tp_grid 4096: the fast-weight step fused
+    either way (a split launch: in the fold launch, splitk_reduce_kernel), Adam only where the launch stays unsplit - the plain
+    gradient otherwise."""
     N, H, W, C, Kc, R, st, pad = cfg
     be.lib.dyb_set_option(b"rep_split", 1)
     be.lib.dyb_set_option(b"tp_min", 1)
     try:
         be.lib.dyb_set_option(b"tp_grid", 1)
-        assert K.case_conv_wgrad_update(be, N, H, W, C, Kc, R, st, pad, seed=sum(cfg)) == 1
-        assert K.case_conv_wgrad_adam(be, N, H, W, C, Kc, R, st, pad, seed=sum(cfg) + 2) == 1       # "fuse_adam": Adam from the accumulators
+        assert K.case_conv_wgrad_fused(be, *cfg, "fast", True, seed=sum(cfg))["form"] == ("v", 1)
+        assert K.case_conv_wgrad_fused(be, *cfg, "adam", True, seed=sum(cfg) + 2)["form"] == ("v", 1)
         be.lib.dyb_set_option(b"tp_grid", 4096)
-        K.case_conv_wgrad_update(be, N, H, W, C, Kc, R, st, pad, seed=sum(cfg) + 1)
-        K.case_conv_wgrad_adam(be, N, H, W, C, Kc, R, st, pad, seed=sum(cfg) + 3)
+        assert (K.case_conv_wgrad_fused(be, *cfg, "fast", True, seed=sum(cfg) + 1)["form"][1] > 1) == splits
+        assert (K.case_conv_wgrad_fused(be, *cfg, "adam", not splits, seed=sum(cfg) + 3)["form"][1] > 1) == splits
     finally:
         be.lib.dyb_set_option(b"tp_grid", 512)
         be.lib.dyb_set_option(b"rep_split", 0)
@@ -553,14 +554,137 @@ def test_conv_weight_gradient_writes_fast_weights(be, cfg):
 def test_conv_weight_gradient_writes_fast_weights_latency_form(be, cfg, sync):
     """"fuse_fast" for ONE sequence (latency form, igemm_mfma_kernel): the finished weight-gradient tile - unsplit, folded by the fold launch
     (splitk_reduce_kernel: addend + scale * sum of slabs) or, with a counter region in scope, folded in-kernel by the last workgroup to
-    arrive - leaves p_next = p_cur - lr * g; the gradient buffer stays untouched."""
-    import numpy as np
+    arrive - leaves p_next = p_cur - lr * g at the tensor's offset in the scope's range; the gradient arena and every float around the
+    tensor stay untouched.  Adam has no latency form: that scope is declined, the plain gradient arrives."""
     N, H, W, C, Kc, R, st, pad = cfg
+    c_real = 3 if C == 4 else None
     ctr = be.zeros((4096,), dtype=np.uint32)
     if sync:
         assert be.lib.dyb_debug_set_conv_sync(be.ptr(ctr), 4096) == 0
     try:
-        assert K.case_conv_wgrad_update(be, N, H, W, C, Kc, R, st, pad, seed=sum(cfg) + sync) == 1
+        assert K.case_conv_wgrad_fused(be, *cfg, "fast", True, seed=sum(cfg) + sync, c_real=c_real)["form"][0] == "w"
+        assert K.case_conv_wgrad_fused(be, *cfg, "adam", False, seed=sum(cfg) + sync, c_real=c_real)["form"][0] == "w"
     finally:
         be.lib.dyb_debug_set_conv_sync(None, 0)
     assert not np.asarray(be.host(ctr)).any()
+
+
+# ---------------------------------------------------------------------------------------- fused weight updates, every form
+# (id, cfg, tp_grid, in-kernel fold, rule) - rule: what the launch does with a fast-weight / an Adam scope, k = tp_kernel
+#   "epilogue": unsplit; the fast-weight step in the epilogue of every loop form, Adam in the pipelined forms' epilogue only (k >= 2)
+#   "fold_launch": split, slabs added by splitk_reduce_kernel: the fast-weight step rides in it, Adam is declined
+#   "inkernel": split, folded in-kernel (k >= 2) or by the fold launch (k = 1): neither - the in-kernel fold carries no update
+#   "pipe0": a map too small for the pipelined pixel walk (16 / Wo >= Ho): the phased loop at every k - fast fused, Adam declined
+WGRAD_FORMS = [
+    ("unsplit_128x128", (1, 12, 12, 128, 128, 1, 1, 0), 1, False, "epilogue"),
+    ("fold_launch", (1, 12, 12, 128, 128, 1, 1, 0), 4096, False, "fold_launch"),
+    ("inkernel_fold", (1, 12, 12, 128, 128, 3, 1, 1), 4096, True, "inkernel"),
+    ("downsample_1x1_s2", (1, 14, 14, 64, 128, 1, 2, 0), 1, False, "epilogue"),
+    ("ragged_49px", (1, 7, 7, 128, 256, 3, 1, 1), 1, False, "epilogue"),
+    ("tile_256x64", (2, 10, 10, 64, 64, 3, 2, 1), 1, False, "epilogue"),
+    ("stem_c_real3", (1, 20, 20, 4, 64, 7, 2, 3), 1, False, "epilogue"),
+    ("map_4x4", (1, 4, 4, 64, 128, 3, 1, 1), 1, False, "pipe0"),
+    ("map_2x8", (1, 2, 8, 64, 128, 3, 1, 1), 1, False, "pipe0"),
+]
+
+
+def wgrad_expected(rule, k, update):
+    """-> (fused, split) the rule states for loop form k"""
+    if rule == "epilogue":
+        return (update == "fast" or k >= 2), False
+    if rule == "fold_launch":
+        return update == "fast", True
+    if rule == "inkernel":
+        return False, True
+    assert rule == "pipe0"
+    return update == "fast", False
+
+
+def _tp_kernel(be):
+    import ctypes
+    v = ctypes.c_int(0)
+    assert be.lib.dyb_get_option(b"tp_kernel", ctypes.byref(v)) == 0
+    return v.value
+
+
+def _stat_folds(be):
+    import ctypes
+    v = ctypes.c_int(0)
+    be.lib.dyb_get_option(b"stat_folds", ctypes.byref(v))
+    return v.value
+
+
+@pytest.mark.parametrize("update", ["fast", "adam_t1", "adam_t10", "adam_eps"])
+@pytest.mark.parametrize("form", WGRAD_FORMS, ids=[f[0] for f in WGRAD_FORMS])
+def test_conv_weight_gradient_fused_update_forms(be, throughput_mode, form, update):
+    """Every form the throughput schedule's weight gradient takes under a fast-weight or an Adam scope, with each loop form (tp_kernel
+    2 / 1 / 3): the form it states (fused or the plain gradient, split or not), and for every run (a) the plain gradient against a
+    float64 torch gradient, (b) fused = the streaming kernel on that gradient, bit for bit, (c) against the float64 restatement of the
+    update; the tensor sits inside a larger scope range whose other floats must not move (kernel_cases.case_conv_wgrad_fused)."""
+    name, cfg, tp_grid, inkernel, rule = form
+    upd, regime = (update, "t10") if update == "fast" else ("adam", update[5:])
+    k = _tp_kernel(be)
+    fused, split = wgrad_expected(rule, k, upd)
+    c_real = 3 if cfg[3] == 4 else None
+    ctr = be.zeros((1024,), dtype=np.uint32)
+    be.lib.dyb_set_option(b"tp_grid", tp_grid)
+    if inkernel:
+        be.lib.dyb_set_option(b"tp_fold", 7)
+        assert be.lib.dyb_debug_set_conv_sync(be.ptr(ctr), 1024) == 0
+    folds = _stat_folds(be)
+    try:
+        r = K.case_conv_wgrad_fused(be, *cfg, upd, fused, seed=sum(cfg) + tp_grid, regime=regime, c_real=c_real)
+    finally:
+        be.lib.dyb_set_option(b"tp_grid", 512)
+        be.lib.dyb_set_option(b"tp_fold", 0)
+        be.lib.dyb_debug_set_conv_sync(None, 0)
+    assert r["form"][0] == "v" and (r["form"][1] > 1) == split, r["form"]
+    if inkernel:
+        assert not np.asarray(be.host(ctr)).any(), "arrival counters not back at zero"
+        assert (_stat_folds(be) - folds == 2) == (k >= 2), "the in-kernel fold was (not) taken"     # (the plain and the scoped launch)
+
+
+def test_conv_weight_gradient_fused_update_declines_a_scope_one_float_short(be, throughput_mode):
+    """A scope range that ends one float before the tensor does: no launch may fuse - the plain gradient arrives, every weight arena
+    stays untouched, no span is reported."""
+    cfg = (1, 12, 12, 128, 128, 1, 1, 0)
+    be.lib.dyb_set_option(b"tp_grid", 1)
+    try:
+        for upd in ("fast", "adam"):
+            assert K.case_conv_wgrad_fused(be, *cfg, upd, False, seed=5, short=True)["form"] == ("v", 1)
+    finally:
+        be.lib.dyb_set_option(b"tp_grid", 512)
+
+
+@pytest.mark.parametrize("update", ["fast", "adam"])
+@pytest.mark.parametrize("cfg", [(1, 12, 12, 128, 128, 1, 1, 0), (1, 7, 7, 128, 256, 3, 1, 1), (2, 10, 10, 64, 64, 3, 2, 1)])
+def test_conv_weight_gradient_fused_update_bf16(be, throughput_mode, cfg, update):
+    """Option "bf16" (operands rounded to bf16 as staged, fp32 accumulate): the pipelined forms fuse both updates (bf16 exists for the
+    pipelined loop only); with tp_kernel 1 the launch goes to the latency form, which leaves bf16 gradients plain.  (a) against the
+    convolution of the bf16-rounded operands, (b) bit for bit."""
+    k = _tp_kernel(be)
+    be.lib.dyb_set_option(b"tp_grid", 1)
+    try:
+        r = K.case_conv_wgrad_fused(be, *cfg, update, k >= 2, seed=sum(cfg) + 11, regime="t10", bf16=True)
+    finally:
+        be.lib.dyb_set_option(b"tp_grid", 512)
+    assert r["form"] == (("v", 1) if k >= 2 else ("w", 1)), r["form"]
+
+
+LINEAR_CASES = [
+    # B, I, O, T, ldw      (linear_outer_kernel's workgroup tile: 32 rows x 256 columns - none of these is a multiple of it)
+    (1, 300, 45, 1, None),
+    (1, 300, 45, 3, None),
+    (2, 556, 70, 2, None),
+    (1, 300, 45, 2, 308),            # I != ldw: not one contiguous tensor - never fused
+]
+
+
+@pytest.mark.parametrize("update", ["fast", "adam_t1", "adam_t10", "adam_eps"])
+@pytest.mark.parametrize("cfg", LINEAR_CASES, ids=["T1", "T3", "B2T2", "ldw"])
+def test_linear_weight_gradient_fused_update(be, cfg, update):
+    """linear_outer_kernel kinds 1 (fast weights) and 2 (Adam) - the regressor's fc1 / fc2 / decoder matrices under a scope: the same
+    checks as the conv cases (kernel_cases.case_linear_wgrad_fused); the bias gradient still written plainly."""
+    B, I, O, T, ldw = cfg
+    upd, regime = (update, "t10") if update == "fast" else ("adam", update[5:])
+    K.case_linear_wgrad_fused(be, B, I, O, T, upd, ldw is None, ldw=ldw, seed=B + I + O + T, regime=regime)

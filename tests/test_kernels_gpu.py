@@ -420,26 +420,26 @@ def test_hmr_exact_hessian_vector_product(be, ckpt_rand, side):
     print(K.case_hmr_hvp(be, ckpt_rand, side=side))
 
 
-@pytest.mark.parametrize("cfg", [
-    (1, 7, 7, 128, 256, 3, 1, 1),      # 49-pixel reduction (ragged last K-step), 128x128 tiles
-    (1, 12, 12, 128, 128, 1, 1, 0),    # 1x1
-    (2, 10, 10, 64, 64, 3, 2, 1),      # Cout = 64: the 256x64 form, stride 2, batch 2
-    (1, 14, 14, 64, 128, 1, 2, 0),     # 1x1 stride 2 (downsample)
-])
-def test_conv_weight_gradient_writes_fast_weights(be, cfg):
-    """"fuse_fast": the throughput-form weight gradient with a weight-update scope in force (kernel_cases.case_conv_wgrad_update) -
-    unsplit (tp_grid 1): p_next = p_cur - lr * g from the epilogue, the gradient buffer untouched; split (tp_grid 4096 where the shape
-    allows a split): the scope is ignored and the plain gradient arrives."""
-    N, H, W, C, Kc, R, st, pad = cfg
+@pytest.mark.parametrize("cfg,splits", [
+    ((1, 7, 7, 128, 256, 3, 1, 1), False),      # 49-pixel reduction (ragged last K-step), 128x128 tiles: too short to split
+    ((1, 12, 12, 128, 128, 1, 1, 0), True),     # 1x1, 144 pixels: split in two at tp_grid 4096
+    ((2, 10, 10, 64, 64, 3, 2, 1), False),      # Cout = 64: the 256x64 form, stride 2, batch 2
+    ((1, 14, 14, 64, 128, 1, 2, 0), False),     # 1x1 stride 2 (downsample)
+], ids=["cfg0", "cfg1", "cfg2", "cfg3"])
+def test_conv_weight_gradient_writes_fast_weights(be, cfg, splits):
+    """"fuse_fast" / "fuse_adam": the throughput-form weight gradient (default loop form) with a weight-update scope in force
+    (kernel_cases.case_conv_wgrad_fused) - unsplit (tp_grid 1): both fused in the epilogue; tp_grid 4096: the fast-weight step fused
+    either way (a split launch: in the fold launch, splitk_reduce_kernel), Adam only where the launch stays unsplit - the plain
+    gradient otherwise."""
     be.lib.dyb_set_option(b"rep_split", 1)
     be.lib.dyb_set_option(b"tp_min", 1)
     try:
         be.lib.dyb_set_option(b"tp_grid", 1)
-        assert K.case_conv_wgrad_update(be, N, H, W, C, Kc, R, st, pad, seed=sum(cfg)) == 1
-        assert K.case_conv_wgrad_adam(be, N, H, W, C, Kc, R, st, pad, seed=sum(cfg) + 2) == 1       # "fuse_adam": Adam from the accumulators
+        assert K.case_conv_wgrad_fused(be, *cfg, "fast", True, seed=sum(cfg))["form"] == ("v", 1)
+        assert K.case_conv_wgrad_fused(be, *cfg, "adam", True, seed=sum(cfg) + 2)["form"] == ("v", 1)
         be.lib.dyb_set_option(b"tp_grid", 4096)
-        K.case_conv_wgrad_update(be, N, H, W, C, Kc, R, st, pad, seed=sum(cfg) + 1)
-        K.case_conv_wgrad_adam(be, N, H, W, C, Kc, R, st, pad, seed=sum(cfg) + 3)
+        assert (K.case_conv_wgrad_fused(be, *cfg, "fast", True, seed=sum(cfg) + 1)["form"][1] > 1) == splits
+        assert (K.case_conv_wgrad_fused(be, *cfg, "adam", not splits, seed=sum(cfg) + 3)["form"][1] > 1) == splits
     finally:
         be.lib.dyb_set_option(b"tp_grid", 512)
         be.lib.dyb_set_option(b"rep_split", 0)
@@ -456,14 +456,92 @@ def test_conv_weight_gradient_writes_fast_weights(be, cfg):
 def test_conv_weight_gradient_writes_fast_weights_latency_form(be, cfg, sync):
     """"fuse_fast" for ONE sequence (latency form, igemm_mfma_kernel): the finished weight-gradient tile - unsplit, folded by the fold launch
     (splitk_reduce_kernel: addend + scale * sum of slabs) or, with a counter region in scope, folded in-kernel by the last workgroup to
-    arrive - leaves p_next = p_cur - lr * g; the gradient buffer stays untouched."""
-    import numpy as np
-    N, H, W, C, Kc, R, st, pad = cfg
+    arrive - leaves p_next = p_cur - lr * g at the tensor's offset in the scope's range; the gradient arena and every float around the
+    tensor stay untouched.  Adam has no latency form: that scope is declined, the plain gradient arrives."""
+    c_real = 3 if cfg[3] == 4 else None
     ctr = be.zeros((4096,), dtype=np.uint32)
     if sync:
         assert be.lib.dyb_debug_set_conv_sync(be.ptr(ctr), 4096) == 0
     try:
-        assert K.case_conv_wgrad_update(be, N, H, W, C, Kc, R, st, pad, seed=sum(cfg) + sync) == 1
+        assert K.case_conv_wgrad_fused(be, *cfg, "fast", True, seed=sum(cfg) + sync, c_real=c_real)["form"][0] == "w"
+        assert K.case_conv_wgrad_fused(be, *cfg, "adam", False, seed=sum(cfg) + sync, c_real=c_real)["form"][0] == "w"
     finally:
         be.lib.dyb_debug_set_conv_sync(None, 0)
     assert not np.asarray(be.host(ctr)).any()
+
+
+# ---------------------------------------------------------------------------------------- fused weight updates at the real sizes
+WGRAD_REGIMES = ["t1", "t10", "eps"]
+# stem, 3x3 s1, 3x3 s2, 1x1 s2, 7x7 stage 4: the other loop forms (tp_kernel 1 / 3) and bf16 on these
+WGRAD_SUBSET = [RESNET_SHAPES[0], RESNET_SHAPES[2], RESNET_SHAPES[6], RESNET_SHAPES[8], RESNET_SHAPES[22]]
+
+
+@pytest.fixture
+def throughput_schedule(be):
+    """throughput schedule for plain calls; the test sets tp_kernel / tp_grid, restored here"""
+    be.lib.dyb_set_option(b"rep_split", 1)
+    be.lib.dyb_set_option(b"tp_min", 1)
+    yield
+    be.lib.dyb_set_option(b"tp_kernel", 2)
+    be.lib.dyb_set_option(b"tp_grid", 512)
+    be.lib.dyb_set_option(b"rep_split", 0)
+    be.lib.dyb_set_option(b"tp_min", 8)
+
+
+def _wgrad_fused_case(be, shape, tp_kernel, tp_grid, update, seed, bf16=False):
+    """One weight gradient of `shape` (batch 1) under a scope, with the form it must take: the fast-weight step fused in every loop form
+    (unsplit: the epilogue; split: the fold launch); Adam fused by the pipelined forms (tp_kernel >= 2) on unsplit launches only.
+    tp_grid 1 must not split; at the default tp_grid the split count is the policy's (read from the plain launch)."""
+    H, W, C, Kc, R, st, pad = shape
+    be.lib.dyb_set_option(b"tp_kernel", tp_kernel)
+    be.lib.dyb_set_option(b"tp_grid", tp_grid)
+    upd = "fast" if update == "fast" else "adam"
+    expect = True if upd == "fast" else (lambda form: tp_kernel >= 2 and form[1] == 1)
+    r = K.case_conv_wgrad_fused(be, 1, H, W, C, Kc, R, st, pad, upd, expect, seed=seed, regime=WGRAD_REGIMES[seed % 3],
+                                c_real=3 if C == 4 else None, bf16=bf16)
+    assert r["form"][0] == "v" and (tp_grid > 1 or r["form"][1] == 1), r["form"]
+    return r
+
+
+@pytest.mark.parametrize("update", ["fast", "adam"])
+@pytest.mark.parametrize("tp_grid", [1, 512])
+@pytest.mark.parametrize("shape", RESNET_SHAPES)
+def test_conv_weight_gradient_fused_update_all_resnet_shapes(be, throughput_schedule, shape, tp_grid, update):
+    """Every ResNet-50 weight gradient the headline run makes under a fast-weight / an Adam scope (tp_kernel 2), unsplit and at the
+    default split policy: the form it takes, (a) the plain gradient against float64, (b) fused = streaming bit for bit, (c) against
+    the float64 update, nothing outside the tensor's span touched (kernel_cases.case_conv_wgrad_fused)."""
+    print(_wgrad_fused_case(be, shape, 2, tp_grid, update, seed=sum(shape) + tp_grid))
+
+
+@pytest.mark.parametrize("update", ["fast", "adam"])
+@pytest.mark.parametrize("tp_grid", [1, 512])
+@pytest.mark.parametrize("tp_kernel", [1, 3], ids=["phased", "pipelined2"])
+@pytest.mark.parametrize("shape", WGRAD_SUBSET)
+def test_conv_weight_gradient_fused_update_loop_forms(be, throughput_schedule, shape, tp_kernel, tp_grid, update):
+    """The same on the stem, a 3x3 s1, a 3x3 s2, a 1x1 s2 and a 7x7 stage-4 shape with the other loop forms: tp_kernel 1 (phased: the
+    fast-weight step fused, Adam declined - the plain gradient for the streaming pass) and 3 (pipelined, two K-steps in flight)."""
+    print(_wgrad_fused_case(be, shape, tp_kernel, tp_grid, update, seed=sum(shape) + tp_grid + tp_kernel))
+
+
+@pytest.mark.parametrize("update", ["fast", "adam"])
+@pytest.mark.parametrize("shape", WGRAD_SUBSET)
+def test_conv_weight_gradient_fused_update_bf16(be, throughput_schedule, shape, update):
+    """Option "bf16" on the subset, unsplit, pipelined loop: both updates fused, bit for bit with the streaming kernels on the bf16
+    launch's own gradient (itself against the float64 convolution of the bf16-rounded operands)."""
+    print(_wgrad_fused_case(be, shape, 2, 1, update, seed=sum(shape) + 7, bf16=True))
+
+
+@pytest.mark.parametrize("update", ["fast", "adam_t1", "adam_t10", "adam_eps"])
+@pytest.mark.parametrize("cfg", [
+    # B, I, O, T, ldw
+    (1, 2208, 1024, 3, None),        # fc1 ([1024][2208]: 2205 inputs padded to a multiple of 4)
+    (1, 1024, 1024, 2, None),        # fc2
+    (1, 1024, 160, 1, None),         # the decoder (decpose / decshape / deccam: one [160][1024] matrix)
+    (1, 2204, 1024, 2, 2208),        # I != ldw: never fused
+], ids=["fc1", "fc2", "decoder", "ldw"])
+def test_linear_weight_gradient_fused_update_real_sizes(be, cfg, update):
+    """linear_outer_kernel kinds 1 / 2 at the regressor's sizes (kernel_cases.case_linear_wgrad_fused): the form, (a) - (c), the span's
+    neighbours untouched, the bias gradient written plainly."""
+    B, I, O, T, ldw = cfg
+    upd, regime = (update, "t10") if update == "fast" else ("adam", update[5:])
+    print(K.case_linear_wgrad_fused(be, B, I, O, T, upd, ldw is None, ldw=ldw, seed=I + O + T, regime=regime))
