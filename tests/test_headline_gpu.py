@@ -11,6 +11,7 @@ import torch
 
 from conftest import golden, rel_err
 from test_adaptation_gpu import assert_final_state_matches_golden, assert_first_frame_outer_gradient
+from stream_evidence import StreamEvidence
 
 pytestmark = pytest.mark.gpu
 
@@ -81,8 +82,11 @@ def test_headline_schedule_stream_matches_reference_and_single_runs(S, headline_
     ads = [_mk(r) for r in range(S)]
     theta0 = ads[0].model.module.theta.detach().clone()
     grp = NS.ReplicaGroup(ads, NF)
+    ev = StreamEvidence(ads[0], "fo_inner3_frameonly", theta0)       # replica 0 frame by frame: fused Adam in the epilogue from t = 1
     for step in range(NF):
+        ev.begin_frame()
         grp.step([frames[r][step] for r in range(S)], step)
+        ev.end_frame(step)
         # replica 0 against the reference's run, frame by frame
         up = float(grp.stepper.losses(step, 3, 0)[3])
         assert abs(up - g["upper_loss"][step]) < 1e-4 * abs(g["upper_loss"][step]), (step, up, g["upper_loss"][step])
@@ -98,6 +102,8 @@ def test_headline_schedule_stream_matches_reference_and_single_runs(S, headline_
         assert abs(float(np.mean(fl[0]["mpjpe"][step])) - g["mpjpe"][step]) < 1e-3 * g["mpjpe"][step]
         assert abs(float(np.mean(fl[0]["pampjpe"][step])) - g["pampjpe"][step]) < 2e-3 * g["pampjpe"][step]
         assert abs(float(np.ravel(fl[0]["pve"])[step]) - g["pve"][step]) < 1e-3 * g["pve"][step]
+    ev.report()
+    assert ev.steps_checked == NF
     # (the throughput schedule sums in another order than the reference AND than a sequence alone: same class-pooled fp32 floor)
     assert_final_state_matches_golden(ads[0], g, theta0, {}, tag="fo_inner3_frameonly")
     # every replica against itself adapted alone: summation order differs (replica-aware split, chunked GroupNorm), arithmetic not

@@ -8,6 +8,7 @@ import torch
 from conftest import cosine, golden, noise_bounds, rel_err
 from oracle import ref_cpu as O
 from dynaboa_amd import assets
+from stream_evidence import Evidence
 
 FRAME_ONLY = dict(retrieval=0, lower_level_mixtrain=0, upper_level_mixtrain=0, use_meanteacher=0,
                   use_motion=0, dynamic_boa=0, use_temporal_losses_upper=0)
@@ -44,8 +45,23 @@ def test_stream(tag, gmm_t, smpl_tabs):
     ad, sd0 = build(opts, ident, gmm_t, smpl_tabs)
     n = int(g["nframes"])
     torch.set_num_threads(8)
+    names = [str(x) for x in g["names"]]
+    # frame by frame (tests/stream_evidence.py): the outer gradient of every Adam step and the state after every frame, at factor 5
+    ev = Evidence(tag, factor=5.0)
+    adam_step = ad.adam_step
+
+    def checked_adam_step(grads):
+        ev.check_gradient(ad.adam_t, np.array([float(grads[k].double().norm()) for k in names]),
+                          {k: grads[k].flatten()[:256].double().numpy() for k in SLICE_PARAMS})
+        return adam_step(grads)
+    ad.adam_step = checked_adam_step
     for step in range(n):
         rec = ad.adapt_frame(assets.make_frame(step, 1, seed=22))
+        fr = dict(m={k: ad.m[k] for k in names}, v={k: ad.v[k] for k in names},
+                  d={k: ad.theta[k].detach() - sd0[k] for k in names})
+        if ad.o["use_meanteacher"]:
+            fr["t"] = {k: ad.teacher[k] - sd0[k] for k in names}
+        ev.check_frame(step, {q: np.array([float(x[k].double().norm()) for k in names]) for q, x in fr.items()})
         if "gated" in tag:
             # every check of the gate: same count, 1 - cos on the reference's side of the threshold with half its distance to spare, within 1 %
             assert len(rec["gate_cos12"]) == int(g["gate_checks"][step]), (step, rec["gate_cos12"])
@@ -58,8 +74,8 @@ def test_stream(tag, gmm_t, smpl_tabs):
         assert rec["extra_steps"] == int(g["extra_steps"][step])
         for k in ("rotmat", "shape", "cam", "joints"):
             assert rel_err(rec["pred"][k], g[f"pred{step}_{k}"]) < 1e-4, (step, k)
-    assert ad.adam_t == int(g["adam_steps"])
-    names = [str(x) for x in g["names"]]
+    assert ad.adam_t == int(g["adam_steps"]) == ev.steps_checked
+    ev.report()
     dn = np.array([float((ad.theta[k].detach().double() - sd0[k].double()).norm()) for k in names])
     mn = np.array([float(ad.m[k].double().norm()) for k in names])
     vn = np.array([float(ad.v[k].double().norm()) for k in names])

@@ -213,6 +213,7 @@ def test_gated_reference_stream_as_replica_0_of_a_group_of_8(tag):
     different summation order than the reference's and than a sequence alone."""
     from conftest import golden
     from test_adaptation_gpu import assert_final_state_matches_golden, assert_gate_matches_golden
+    from stream_evidence import StreamEvidence
     from dynaboa_amd import assets, native_step as NS, _lib
     g = golden(f"g5_{tag}.npz")
     S, NF = 8, int(g["nframes"])
@@ -227,9 +228,12 @@ def test_gated_reference_stream_as_replica_0_of_a_group_of_8(tag):
         theta0 = ads[0].model.module.theta.detach().clone()
         grp = NS.ReplicaGroup(ads, NF)
         assert grp.stepper.full and grp.stepper.S == S
+        ev = StreamEvidence(ads[0], tag, theta0)      # replica 0 frame by frame (tests/stream_evidence.py)
         worst = 0.0
         for s in range(NF):
+            ev.begin_frame()
             grp.step([frames[r][s] for r in range(S)], s)
+            ev.end_frame(s)
             worst = max(worst, assert_gate_matches_golden(ads[0], g, s))
             up = float(ads[0].fit_losses["ul/total"])
             assert abs(up - g["upper_loss"][s]) < 1e-4 * abs(g["upper_loss"][s]), (s, up, g["upper_loss"][s])
@@ -238,6 +242,7 @@ def test_gated_reference_stream_as_replica_0_of_a_group_of_8(tag):
         lib.dyb_set_option(b"rep_split", 0)
         lib.dyb_set_option(b"tp_min", 8)
     print("gate %s, replica 0 of 8: worst |d(1 - cos12)| as a fraction of the check's distance from the threshold %.3f (margin %.2e)" % (tag, worst, float(g["gate_margin"])))
+    ev.report()
     steps = [int(x) for x in g["extra_steps"]]
     assert list(ads[0].optim_step_record) == steps
     assert len({tuple(a.optim_step_record) for a in ads}) > 1           # the sequences of the group took different paths

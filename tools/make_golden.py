@@ -12,7 +12,8 @@ whose *semantics* matter are supplied explicitly below:
             the seeded synthetic tables of dynaboa_amd.assets.make_synthetic_smpl
 so the goldens pin every line of arithmetic that lives in /root/reference, driven end to end.
 
-usage:  PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py [--only g1,g3] [--out tests/golden]
+usage:  PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py [--only g1,g3] [--out tests/golden] [--verify-existing]
+        (--verify-existing: a g5 stream is written only if every key of the committed file comes back identical, NaN == NaN)
 """
 from __future__ import annotations
 
@@ -324,11 +325,78 @@ def gate_checks(a, step):
     return np.array([[chk[i]["cos"] for i in range(len(chk))] for chk in a.feat_sims.get(step, [])], dtype=np.float64)
 
 
+# the slices the stream tests compare (tests/test_adaptation_gpu.py SLICE_PARAMS): per Adam step, the first 256 outer-gradient elements
+STEP_SLICE_PARAMS = ["conv1.weight", "layer1.0.conv2.weight", "layer2.0.conv2.weight", "layer3.5.conv1.weight",
+                     "layer4.0.conv2.weight", "layer4.2.bn3.weight", "fc1.weight", "fc2.weight", "decpose.weight",
+                     "decpose.bias", "deccam.bias"]
+
+
+def record_adam_steps(a, names, hook=None):
+    """Wrap the reference adaptor's optimizer.step (dynaboa_benchmark.py:151,179,199): before every Adam step, record the outer gradient
+    it is about to apply - p.grad, which under learn2learn first_order=False already is the second-order gradient - as per-tensor
+    float64 norms and the first 256 elements of STEP_SLICE_PARAMS.  a.adam_log = dict(norms=[], frame=[], slices={name: []}); `hook`
+    (if given) is called with {name: grad} first (tools/make_noise.py compares the full tensors).  The step itself is untouched."""
+    orig = a.optimizer.step
+    params = list(a.model.module.parameters())
+    a.adam_log = dict(norms=[], frame=[], slices={n: [] for n in STEP_SLICE_PARAMS})
+
+    def step(*args, **kw):
+        gr = {n: (p.grad.detach() if p.grad is not None else torch.zeros_like(p)) for n, p in zip(names, params)}
+        if hook is not None:
+            hook(gr)
+        a.adam_log["norms"].append([float(gr[n].double().norm()) for n in names])
+        a.adam_log["frame"].append(int(a.global_step))
+        for n in STEP_SLICE_PARAMS:
+            a.adam_log["slices"][n].append(gr[n].flatten()[:256].float().numpy().copy())
+        return orig(*args, **kw)
+    a.optimizer.step = step
+
+
+def frame_state(a, names, theta0):
+    """-> per-tensor float64 norms of exp_avg, exp_avg_sq, theta - theta0 (and the teacher's drift where there is one)."""
+    st = a.optimizer.state
+    pm = dict(zip(names, a.model.module.parameters()))
+    out = dict(m=[float(st[pm[n]]["exp_avg"].double().norm()) for n in names],
+               v=[float(st[pm[n]]["exp_avg_sq"].double().norm()) for n in names],
+               d=[float((pm[n].detach().double() - theta0[n].double()).norm()) for n in names])
+    if getattr(a, "teacher", None) is not None and a.options.use_meanteacher:
+        tm = dict(a.teacher.named_parameters())
+        out["t"] = [float((tm[n].detach().double() - theta0[n].double()).norm()) for n in names]
+    return out
+
+
+def verify_existing(path, payload):
+    """Every key of the committed file `path` must come back with identical values (NaN == NaN); raises before anything is written."""
+    if not os.path.exists(path):
+        print(f"verify-existing: {os.path.basename(path)} is new")
+        return
+    old = np.load(path, allow_pickle=False)
+    bad = []
+    for k in old.files:
+        if k not in payload:
+            bad.append((k, "missing"))
+            continue
+        x, y = old[k], np.asarray(payload[k])
+        if x.shape != y.shape or x.dtype.kind != y.dtype.kind:
+            bad.append((k, f"shape/dtype {x.shape} {x.dtype} -> {y.shape} {y.dtype}"))
+        elif not np.array_equal(x, y, equal_nan=x.dtype.kind in "fc"):
+            bad.append((k, "values"))
+    if bad:
+        raise SystemExit(f"verify-existing: {os.path.basename(path)} NOT reproduced on this host, file left as it is: {bad[:10]}")
+    print(f"verify-existing: {os.path.basename(path)}: all {len(old.files)} committed keys identical; "
+          f"{len(set(payload) - set(old.files))} new keys")
+
+
+VERIFY_EXISTING = False
+
+
 def run_stream(tag, out, opts_over, nframes, identity_pose=False, first_order=True, extra_payload=None):
     a, sd0 = make_ref_adaptor(opts_over, identity_pose=identity_pose, first_order=first_order)
     record_exact_cosines(a)
     names = [n for n, _ in a.model.module.named_parameters()]
     theta0 = {n: p.detach().clone() for n, p in a.model.module.named_parameters()}
+    record_adam_steps(a, names)
+    per_frame = []
     rec = dict(lower=[], upper=[], mpjpe=[], pampjpe=[], pve=[], steps=[])
     preds = []
     for step in range(nframes):
@@ -343,6 +411,7 @@ def run_stream(tag, out, opts_over, nframes, identity_pose=False, first_order=Tr
         rec["upper"].append(float(a.fit_losses.get("ul/unlabelloss", float("nan"))))
         rec["steps"].append(a.optim_step_record[-1] if a.optim_step_record else 0)
         rec.setdefault("gate", []).append(gate_checks(a, step))
+        per_frame.append(frame_state(a, names, theta0))
         with torch.no_grad():
             r, s, c = a.model(batch["image"])
             so = a.decode_smpl_params(r, s)
@@ -372,6 +441,14 @@ def run_stream(tag, out, opts_over, nframes, identity_pose=False, first_order=Tr
         payload["m_" + n] = head(st[pmap[n]]["exp_avg"])
         payload["v_" + n] = head(st[pmap[n]]["exp_avg_sq"])
     payload.update(first)
+    # per Adam step (the outer gradient it applied) and per frame (the state after it): tests/stream_evidence.py
+    payload.update(gstep_norms=np.array(a.adam_log["norms"]), step_frame=np.array(a.adam_log["frame"]),
+                   frame_m_norms=np.array([f["m"] for f in per_frame]), frame_v_norms=np.array([f["v"] for f in per_frame]),
+                   frame_delta_norms=np.array([f["d"] for f in per_frame]))
+    for n in STEP_SLICE_PARAMS:
+        payload["gstep_" + n] = np.stack(a.adam_log["slices"][n]).astype(np.float32)
+    if "t" in per_frame[0]:
+        payload["frame_teacher_delta_norms"] = np.array([f["t"] for f in per_frame])
     if a.options.dynamic_boa and a.options.use_boa:
         # every check of the gate: cos of the 15 features, NaN where the loop had already left; gate_1mcos12 = what the while
         # condition compares with the threshold (python double of 1 - fp32 cosine, dynaboa_benchmark.py:169)
@@ -398,6 +475,9 @@ def run_stream(tag, out, opts_over, nframes, identity_pose=False, first_order=Tr
         tmap = dict(a.teacher.named_parameters())
         payload["teacher_delta_norms"] = np.array(
             [float((tmap[n].detach().double() - theta0[n].double()).norm()) for n in names])
+    assert len(payload["step_frame"]) == payload["adam_steps"], (len(payload["step_frame"]), payload["adam_steps"])
+    if VERIFY_EXISTING:
+        verify_existing(os.path.join(out, f"g5_{tag}.npz"), payload)
     np.savez_compressed(os.path.join(out, f"g5_{tag}.npz"), **payload)
     print(f"g5 {tag} ok", rec["upper"], rec["steps"])
     return payload
@@ -610,7 +690,10 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
     ap.add_argument("--gate_threshold", type=float, default=None, help="g5_gated: skip the search and use this threshold")
     ap.add_argument("--gate_tag", default="fo_inner1_full_gated", help="g5_gated: name of the golden (g5_<tag>.npz)")
+    ap.add_argument("--verify-existing", action="store_true",
+                    help="g5 streams: before writing g5_<tag>.npz, assert every key of the committed file comes back identical")
     args = ap.parse_args()
+    VERIFY_EXISTING = args.verify_existing
     os.makedirs(args.out, exist_ok=True)
     torch.manual_seed(0)
     torch.set_num_threads(8)
