@@ -11,6 +11,12 @@ dynaboa_benchmark.py:126-157 (initial feature forward, inference() after every i
 the outer step: 9 forwards + 4 backwards + 13 SMPL forwards per frame); nothing is skipped.
 Each rank owns an independent replica + stream shard (weak scaling, no data-path collective;
 SURVEY 8e); rank 0 prints ONE JSON line.
+
+A plain run does what the headline needs and nothing else: set up, warm up, time the steps, write
+--dump-outputs, print the line.  --full adds every other measurement, outside the headline's clock:
+the conv roofline pass, the per-step percentile pass, the PCIe-inclusive pass, the sequences-per-GPU
+sweep, the side configurations (each in a fresh process), the CPU baseline and, with N > 1 ranks,
+the 3DPW operating point.  The --no_* switches and --percentile_frames trim a --full run.
 """
 from __future__ import annotations
 
@@ -596,6 +602,9 @@ def main():
     ap.add_argument("--second_order", type=int, default=0,
                     help="1: second-order MAML (BASELINE config 5's ablation arm); the reference and the default run are first-order")
     ap.add_argument("--hvp", choices=["fd", "exact"], default="exact", help="second order: exact (tangent passes) or finite-difference Hessian-vector products")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline (roofline, percentile and PCIe-inclusive passes, sequences-per-GPU sweep, "
+                         "side configurations, CPU baseline; with --gpus N > 1 the 3DPW operating point)")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_roofline", action="store_true")
     ap.add_argument("--no_sub_records", action="store_true", help="skip the second-order / batch-8 / full-loss-set side runs")
@@ -622,6 +631,8 @@ def main():
                     help="after the timed steps write what their last step computed (predictions, errors, a sample of the adapted weights) "
                          "as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if (args.conv_table or args.all_sub_records) and not args.full:
+        ap.error("--conv_table and --all_sub_records belong to the --full run")
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline_worker(args.inner_step)))
         return
@@ -669,11 +680,12 @@ def main():
     # replica groups cover the first-order configurations: frame losses (the headline) and, given explicitly, the default term set
     seqs = args.seqs if (simple or (args.full_losses and not args.second_order and args.seqs_full)) else 1
     total = args.warmup + args.steps
-    n_roof = 0 if args.no_roofline else 4           # extra steps for the instrumented roofline pass (outside the clock)
-    n_pct = args.percentile_frames if (args.steps < 200 and args.percentile_frames > 0) else 0
+    # the extra passes below run with --full only; a plain run builds the frames of its warm-up and timed steps and no more
+    n_roof = 4 if (args.full and not args.no_roofline) else 0      # extra steps for the instrumented roofline pass (outside the clock)
+    n_pct = args.percentile_frames if (args.full and args.steps < 200 and args.percentile_frames > 0) else 0
     # extra steps of the PCIe-inclusive pass (outside the clock): as many timed steps as the headline (round 6: it used to time 5 steps, whose
     # end-of-run metric flush and drain weighed four times as much as in the headline's 20)
-    n_h2d = 0 if (args.no_sub_records or not simple or args.groups > 1) else max(6, min(args.steps, 40) + 1)
+    n_h2d = max(6, min(args.steps, 40) + 1) if (args.full and not args.no_sub_records and simple and args.groups <= 1) else 0
     nfr = total + n_roof + n_pct + n_h2d
     rn = Runner(device, seqs, args.batch, args.inner_step, nfr, rank=rank, groups=args.groups, full_losses=args.full_losses,
                 second_order=args.second_order, share_forwards=args.share_forwards, overlap=args.overlap, schedule=args.schedule,
@@ -772,15 +784,15 @@ def main():
                                           ("gloo (DYB_BENCH_SMOKE_ONE_GPU)" if os.environ.get("DYB_BENCH_SMOKE_ONE_GPU") == "1" else "RCCL"))
                           if gathered is not None else None,
                           "engine_graphs": __import__("dynaboa_amd.hmr", fromlist=["get_layout"]).get_layout(args.batch).graph_stats()}}
-        if not args.no_roofline:
+        if n_roof:
             lo = total
             torch.cuda.synchronize()
             r = conv_roofline(run, lo, lo + n_roof, main_stream)
             rn.flush()
-        if not args.no_roofline and r is not None and args.conv_table and r.get("table"):
+        if n_roof and r is not None and args.conv_table and r.get("table"):
             with open(args.conv_table, "w") as f:
                 f.write(r["table"])
-        if not args.no_roofline and r is not None:
+        if n_roof and r is not None:
             tr = pmc_traffic()
             fr = n_roof * seqs
             out["roofline"] = {"bound": "mfma", "achieved": r["achieved"], "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
@@ -846,7 +858,7 @@ def main():
                                              "uploaded from pinned host memory (one stacked buffer per input kind and step) on the issuing stream inside the clock, as the reference moves its "
                                              "batch every frame (dynaboa_benchmark.py:86); `value` above has the inputs resident in HBM"}
             del pinned
-        if world == 1 and not args.no_sub_records and simple and args.batch == 1:
+        if args.full and world == 1 and not args.no_sub_records and simple and args.batch == 1:
             del rn, run, res
             torch.cuda.empty_cache()
             reps = {}
@@ -956,7 +968,7 @@ def main():
                 "test_second_order_full_loss_set_matches_reference_second_order)", full_losses=1, second_order=1, hvp="exact", hvp_terms="all")
     # N > 1: what the real 3DPW test stream can supply - 24 files / ~37 person tracks (utils/data_preprocess/pw3d.py:71-77) shared by
     # N ranks is ceil(37 / N) sequences per GPU, not 32; the same timed loop at that size (all ranks, barrier + max as above)
-    if dist is not None and simple and args.batch == 1 and not args.no_sub_records:
+    if args.full and dist is not None and simple and args.batch == 1 and not args.no_sub_records:
         s_real = -(-37 // world)
         try:
             del rn
@@ -975,7 +987,7 @@ def main():
             if rank == 0:
                 out["pw3d_operating_point"] = dict(value=None, error=f"{type(e).__name__}: {e}")
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:          # reported baseline: rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:          # reported baseline: rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(inner_step=args.inner_step)
         # the literal one-stream readings as scalars right behind `value` (full records further down the line)
         front = ("metric", "value", "unit")

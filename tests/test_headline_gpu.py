@@ -188,8 +188,8 @@ def test_bench_multi_rank_control_flow_on_one_gpu():
     """`bench.py --gpus 2` end to end on this ONE-GPU box (DYB_BENCH_SMOKE_ONE_GPU=1: both ranks on cuda:0, gloo instead of
     RCCL, which refuses two ranks on one device) - the self-spawn through torch.distributed.run, rank / world from the environment,
     barrier + max-over-ranks timing, the ragged end-of-run gather of the per-frame errors (sharding.gather_frame_metrics) and the
-    3DPW operating point at ceil(37 / N) sequences per GPU.  A functional check of the N > 1 path the driver runs on an 8-GPU node,
-    never a measurement."""
+    3DPW operating point at ceil(37 / N) sequences per GPU (a --full measurement).  A functional check of the N > 1 path the driver runs
+    on an 8-GPU node, never a measurement."""
     import json
     import os
     import subprocess
@@ -200,7 +200,7 @@ def test_bench_multi_rank_control_flow_on_one_gpu():
         env.pop(k, None)
     seqs, steps = 3, 2
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "1", "--seqs", str(seqs),
-                          "--no_cpu_baseline", "--no_roofline", "--percentile_frames", "0"],
+                          "--full", "--no_cpu_baseline", "--no_roofline", "--percentile_frames", "0"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -245,6 +245,29 @@ def test_bench_dump_outputs_are_reproducible(tmp_path):
         assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
         assert np.array_equal(a[k], b[k]), k
     assert np.abs(a["adam_m"]).max() > 0                          # the sample holds adapted state, not an untouched arena
+
+
+def test_bench_plain_run_carries_the_headline_only():
+    """`bench.py` without --full: the headline record and nothing that takes a pass, a process or a host measurement of its own - no
+    roofline, percentile, PCIe-inclusive, sweep, side-configuration or CPU-baseline records."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    seqs, steps = 2, 3
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                          "--seqs", str(seqs)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["unit"] == "adapted frames/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32" and rec["steps"] == steps
+    assert abs(rec["value"] - steps * seqs / (rec["ms_per_step"] * 1e-3 * steps)) < 1e-6 * rec["value"]
+    full_only = ("roofline", "frame_time_ms", "pcie_inclusive", "sequences_per_gpu_sweep", "single_stream", "second_order",
+                 "pw3d_operating_point", "batch8_exemplars", "full_default_losses", "cpu_baseline")
+    assert not [k for k in full_only if k in rec], sorted(rec)
+    assert "[bench] side run" not in out.stderr
 
 
 def test_fast_weights_from_the_weight_gradient_epilogue_are_bit_identical_to_the_streaming_pass(headline_switches, monkeypatch):
