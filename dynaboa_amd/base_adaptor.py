@@ -15,6 +15,7 @@ clusters) can be injected through ``assets_bundle`` so the path runs on syntheti
 """
 from __future__ import annotations
 
+import logging
 import os
 import random
 from types import SimpleNamespace
@@ -396,7 +397,14 @@ class BaseAdaptor:
         if not other and getattr(o, f"use_frame_losses_{level}"):
             # frame losses only (the benchmarked second-order configuration): the head's gradient straight from the kernels
             return lambda theta: frame_level_hvp(hmr, self.smpl_neutral, self.gmm_f, theta, image, gt_keypoints_2d, o.s2dloss_weight,
-                                                 o.shape_prior_weight, o.pose_prior_weight)
+                                                 o.shape_prior_weight, o.pose_prior_weight, head=getattr(o, "hvp_head", "fd"))
+        if getattr(o, "hvp_head", "fd") == "closed" and not getattr(self, "_hvp_head_fd_logged", False):
+            # teacher / motion / labelled terms have no closed-form second derivative: the whole level keeps the difference quotient of
+            # its head (never a mix of the two forms inside one level); said once per run
+            self._hvp_head_fd_logged = True
+            logging.getLogger(__name__).warning(
+                "--hvp_head closed: the %s level has teacher / motion / labelled terms; its head keeps the difference quotient "
+                "(--hvp_head fd) - the closed form covers levels made of the frame losses only", level)
         if getattr(o, "hvp_terms", "all") != "all":
             return None                      # --hvp_terms frame: teacher / motion / labelled levels keep the difference quotient
         used = getattr(self, "_last_h36m", None)

@@ -71,6 +71,12 @@ parser.add_argument('--hvp', type=str, default=os.environ.get("DYB_HVP", "exact"
                          'the backbone and regressor; the 157-input loss head (rot6d -> SMPL -> projection / priors) is differentiated '
                          'along the state tangent by a central difference of its analytic gradient (exact: levels made of the frame '
                          'losses; other levels fall back) - or as a central difference of first-order gradients of the whole level (fd)')
+parser.add_argument('--hvp_head', type=str, default=os.environ.get("DYB_HVP_HEAD", "fd"), choices=["fd", "closed"],
+                    help='--second_order 1 --hvp exact only: the second derivative of the 157-input loss head as a central difference of '
+                         'its analytic gradient (fd, the default) or in closed form (closed: one dyb_head_hvp call runs every head kernel '
+                         'on (value, tangent) pairs - with it the whole product H v is exact, no step size anywhere).  Closed covers levels '
+                         'made of the frame losses; a level with teacher / motion / labelled terms keeps fd for its whole head (logged '
+                         'once per run)')
 parser.add_argument('--hvp_terms', type=str, default="all", choices=["all", "frame"],
                     help='--hvp exact for every level through the multi-pass form (all, the default: on MI355X the 4-frame second-order '
                          'stream on the default term set matches the reference\'s first_order=False run element-wise) or only for levels '

@@ -10,6 +10,7 @@
 // rule of exactly that formula (same branch selection), so it matches torch autograd of the
 // reference away from the theta -> 0 singularity (where autograd itself produces inf*0).
 #include "dyb_common.h"
+#include "dyb_dual.h"
 
 #define NJ 24
 #define NJ49 49
@@ -57,6 +58,41 @@ __device__ __forceinline__ void quat_to_aa(const float* q, float* aa) {
     aa[i] = (v != v) ? 0.f : v;
   }
 }
+// gradient of the selected branch of rot_to_quat: dR (9) from the gradients of u (4) and of the trace term
+// index order: r00 0, r01 1, r02 2, r10 3, r11 4, r12 5, r20 6, r21 7, r22 8
+template <class F>
+__device__ __forceinline__ void quat_bwd_scatter(int branch, F gt, const F* gu, F* dR) {
+  switch (branch) {
+    case 0:
+      gt += gu[1];
+      dR[7] += gu[0]; dR[5] -= gu[0];
+      dR[3] += gu[2]; dR[1] += gu[2];
+      dR[2] += gu[3]; dR[6] += gu[3];
+      dR[0] += gt; dR[4] -= gt; dR[8] -= gt;
+      break;
+    case 1:
+      gt += gu[2];
+      dR[2] += gu[0]; dR[6] -= gu[0];
+      dR[3] += gu[1]; dR[1] += gu[1];
+      dR[7] += gu[3]; dR[5] += gu[3];
+      dR[0] -= gt; dR[4] += gt; dR[8] -= gt;
+      break;
+    case 2:
+      gt += gu[3];
+      dR[3] += gu[0]; dR[1] -= gu[0];
+      dR[2] += gu[1]; dR[6] += gu[1];
+      dR[7] += gu[2]; dR[5] += gu[2];
+      dR[0] -= gt; dR[4] -= gt; dR[8] += gt;
+      break;
+    default:
+      gt += gu[0];
+      dR[7] += gu[1]; dR[5] -= gu[1];
+      dR[2] += gu[2]; dR[6] -= gu[2];
+      dR[3] += gu[3]; dR[1] -= gu[3];
+      dR[0] += gt; dR[4] += gt; dR[8] += gt;
+      break;
+  }
+}
 // dR (9) from g = dL/d(aa)
 __device__ __forceinline__ void aa_bwd(const float* R, const float* g, float* dR) {
   QuatFwd f = rot_to_quat(R);
@@ -88,37 +124,111 @@ __device__ __forceinline__ void aa_bwd(const float* R, const float* g, float* dR
   }
   float gt = -0.25f * dot / (f.t * rt);
   for (int i = 0; i < 9; ++i) dR[i] = 0.f;
-  // index order: r00 0, r01 1, r02 2, r10 3, r11 4, r12 5, r20 6, r21 7, r22 8
-  switch (f.branch) {
+  quat_bwd_scatter(f.branch, gt, gu, dR);
+}
+
+// ---- tangents of the rotation-matrix -> axis-angle map and of its gradient (closed-form head Hessian) --------------------------
+// Everything here is evaluated in double on the float inputs (23 joints per sample: the cost is nothing), inside the branches the
+// float primal selects; the primal values themselves always come from the float functions above.
+//
+// aa = v k(w, s2) with q = (w, v), s2 = |v|^2, k = tt / s, tt = 2 atan2(s, w) (both signs of w shift tt by a constant only).
+// First and second partial derivatives of k:
+//     k_w = -2 / den,  k_ww = 4 w / den^2,  k_ws2 = 2 / den^2                    (den = s2 + w^2; smooth everywhere)
+//     k_s2 = (w / den - k / 2) / s2,  k_s2s2 = (-w / den^2 - 3/2 k_s2) / s2      (differences of nearly equal terms as s2 -> 0)
+// With z = s2 / w^2 and w > 0:  k = 2/w a(z),  k_s2 = c(z) / w^3,  k_s2s2 = c'(z) / w^5,
+//     a(z) = sum_n (-1)^n z^n / (2n+1),   c(z) = sum_{n>=1} (-1)^n 2n/(2n+1) z^(n-1).
+// The series (n <= 6) is used for z < 1e-3 (a joint angle below 0.063 rad).  How the threshold was picked: the closed forms lose
+// about eps64 / z^2 = 2e-10 there, the truncated series 5.6 z^5 = 6e-15 - both far inside fp32's 6e-8, so the switch is invisible in
+// the float result, and with z < 1e-3 the series needs no more than six terms.  At s2 = 0 exactly (a joint at the identity) the
+// series is the finite limit (k = 2 / w, k_s2 = -2 / (3 w^3)), consistent with the k = 2 branch of aa_bwd.
+struct AaK {
+  duald k, k_w, k_s2;
+};
+__device__ __forceinline__ AaK aa_k(duald w, duald s2) {
+  const double den = s2.v + w.v * w.v, id2 = 1.0 / (den * den);
+  const double k_w = -2.0 / den, k_ww = 4.0 * w.v * id2, k_ws2 = 2.0 * id2;
+  double k, k_s2, k_s2s2;
+  const double w2 = w.v * w.v;
+  if (w.v > 0.0 && s2.v < 1e-3 * w2) {
+    const double z = s2.v / w2;
+    const double a = 1.0 + z * (-1.0 / 3 + z * (1.0 / 5 + z * (-1.0 / 7 + z * (1.0 / 9 + z * (-1.0 / 11 + z * (1.0 / 13))))));
+    const double c = -2.0 / 3 + z * (4.0 / 5 + z * (-6.0 / 7 + z * (8.0 / 9 + z * (-10.0 / 11 + z * (12.0 / 13)))));
+    const double c1 = 4.0 / 5 + z * (-12.0 / 7 + z * (24.0 / 9 + z * (-40.0 / 11 + z * (60.0 / 13))));
+    k = 2.0 / w.v * a;
+    k_s2 = c / (w2 * w.v);
+    k_s2s2 = c1 / (w2 * w2 * w.v);
+  } else {
+    const double sn = sqrt(s2.v);
+    const double tt = 2.0 * (w.v < 0.0 ? atan2(-sn, -w.v) : atan2(sn, w.v));
+    k = tt / sn;
+    k_s2 = (w.v / den - 0.5 * k) / s2.v;
+    k_s2s2 = (-w.v * id2 - 1.5 * k_s2) / s2.v;
+  }
+  AaK r;
+  r.k = dyb_mk<double>(k, k_s2 * s2.t + k_w * w.t);
+  r.k_w = dyb_mk<double>(k_w, k_ws2 * s2.t + k_ww * w.t);
+  r.k_s2 = dyb_mk<double>(k_s2, k_s2s2 * s2.t + k_ws2 * w.t);
+  return r;
+}
+struct QuatDual {
+  duald t, u[4], q[4];
+};
+__device__ __forceinline__ QuatDual rot_to_quat_dual(const float* R, const float* tR, int branch) {
+  duald r[9];
+  for (int i = 0; i < 9; ++i) r[i] = dyb_mk<double>((double)R[i], (double)tR[i]);
+  QuatDual f;
+  switch (branch) {                  // r00 0, r01 1, r02 2, r10 3, r11 4, r12 5, r20 6, r21 7, r22 8
     case 0:
-      gt += gu[1];
-      dR[7] += gu[0]; dR[5] -= gu[0];
-      dR[3] += gu[2]; dR[1] += gu[2];
-      dR[2] += gu[3]; dR[6] += gu[3];
-      dR[0] += gt; dR[4] -= gt; dR[8] -= gt;
+      f.t = 1.0 + r[0] - r[4] - r[8];
+      f.u[0] = r[7] - r[5]; f.u[1] = f.t; f.u[2] = r[3] + r[1]; f.u[3] = r[2] + r[6];
       break;
     case 1:
-      gt += gu[2];
-      dR[2] += gu[0]; dR[6] -= gu[0];
-      dR[3] += gu[1]; dR[1] += gu[1];
-      dR[7] += gu[3]; dR[5] += gu[3];
-      dR[0] -= gt; dR[4] += gt; dR[8] -= gt;
+      f.t = 1.0 - r[0] + r[4] - r[8];
+      f.u[0] = r[2] - r[6]; f.u[1] = r[3] + r[1]; f.u[2] = f.t; f.u[3] = r[7] + r[5];
       break;
     case 2:
-      gt += gu[3];
-      dR[3] += gu[0]; dR[1] -= gu[0];
-      dR[2] += gu[1]; dR[6] += gu[1];
-      dR[7] += gu[2]; dR[5] += gu[2];
-      dR[0] -= gt; dR[4] -= gt; dR[8] += gt;
+      f.t = 1.0 - r[0] - r[4] + r[8];
+      f.u[0] = r[3] - r[1]; f.u[1] = r[2] + r[6]; f.u[2] = r[7] + r[5]; f.u[3] = f.t;
       break;
     default:
-      gt += gu[0];
-      dR[7] += gu[1]; dR[5] -= gu[1];
-      dR[2] += gu[2]; dR[6] -= gu[2];
-      dR[3] += gu[3]; dR[1] -= gu[3];
-      dR[0] += gt; dR[4] += gt; dR[8] += gt;
+      f.t = 1.0 + r[0] + r[4] + r[8];
+      f.u[0] = f.t; f.u[1] = r[7] - r[5]; f.u[2] = r[2] - r[6]; f.u[3] = r[3] - r[1];
       break;
   }
+  const duald k = 0.5 / dyb_sqrt(f.t);
+  for (int i = 0; i < 4; ++i) f.q[i] = f.u[i] * k;
+  return f;
+}
+// taa (3): tangent of the axis-angle vector along tR
+__device__ __forceinline__ void aa_fwd_tan(const float* R, const float* tR, float* taa) {
+  const QuatDual f = rot_to_quat_dual(R, tR, rot_to_quat(R).branch);
+  const duald s2 = f.q[1] * f.q[1] + f.q[2] * f.q[2] + f.q[3] * f.q[3];
+  const AaK K = aa_k(f.q[0], s2);
+  for (int i = 0; i < 3; ++i) taa[i] = (float)(f.q[1 + i] * K.k).t;
+}
+// tdR (9): tangent of aa_bwd's result along (tR, tg)
+__device__ __forceinline__ void aa_bwd_tan(const float* R, const float* tR, const float* g, const float* tg, float* tdR) {
+  const QuatDual f = rot_to_quat_dual(R, tR, rot_to_quat(R).branch);
+  const duald s2 = f.q[1] * f.q[1] + f.q[2] * f.q[2] + f.q[3] * f.q[3];
+  const AaK K = aa_k(f.q[0], s2);
+  duald gd[3], gq[4];
+  for (int i = 0; i < 3; ++i) gd[i] = dyb_mk<double>((double)g[i], (double)tg[i]);
+  const duald gk = gd[0] * f.q[1] + gd[1] * f.q[2] + gd[2] * f.q[3];
+  gq[0] = gk * K.k_w;
+  const duald m = 2.0 * (gk * K.k_s2);
+  for (int i = 0; i < 3; ++i) gq[1 + i] = gd[i] * K.k + f.q[1 + i] * m;
+  // q = 0.5 * u / sqrt(t)
+  const duald rt = dyb_sqrt(f.t);
+  duald gu[4], dot = dyb_mk<double>(0.0, 0.0);
+  for (int i = 0; i < 4; ++i) {
+    gu[i] = 0.5 * gq[i] / rt;
+    dot += gq[i] * f.u[i];
+  }
+  duald gt = -0.25 * dot / (f.t * rt);
+  duald d[9];
+  for (int i = 0; i < 9; ++i) d[i] = dyb_mk<double>(0.0, 0.0);
+  quat_bwd_scatter(rot_to_quat(R).branch, gt, gu, d);
+  for (int i = 0; i < 9; ++i) tdR[i] = (float)d[i].t;
 }
 
 __global__ __launch_bounds__(64) void rotmat_to_aa_kernel(const float* __restrict__ R, float* __restrict__ aa, int n) {
@@ -333,9 +443,16 @@ struct FrameLossArgs {
   float* djoints;        // [B][49][3]
   int lds, ldc, ldds, lddc, B;
   float w2d, wshape, wpose;
+  // tangent form only (S = dualf): tangents of the four inputs and of the four gradients, each shaped like its value array
+  const float *trot, *tshape, *tcam, *tjoints;
+  float *tdrot, *tdshape, *tdcam, *tdjoints;
 };
 
+// S = float: value and gradient.  S = dualf: also the tangent of the gradient along (trot, tshape, tcam, tjoints), with the
+// quaternion branch and the mixture component the value selects held fixed.
+template <class S>
 __global__ __launch_bounds__(256) void frame_losses_kernel(FrameLossArgs a, DybRep Rp) {
+  typedef DybIO<S> IO;
   DYB_REP_PROLOGUE(Rp);
   if (dyb_rep) {
     a.rot = dyb_rb(a.rot, Rp, dyb_rep); a.shape = dyb_rb(a.shape, Rp, dyb_rep); a.cam = dyb_rb(a.cam, Rp, dyb_rep);
@@ -343,8 +460,10 @@ __global__ __launch_bounds__(256) void frame_losses_kernel(FrameLossArgs a, DybR
     a.drot = dyb_rb(a.drot, Rp, dyb_rep); a.dshape = dyb_rb(a.dshape, Rp, dyb_rep); a.dcam = dyb_rb(a.dcam, Rp, dyb_rep);
     a.djoints = dyb_rb(a.djoints, Rp, dyb_rep);
   }
-  __shared__ float sAA[ND], sD[NG][ND], sRow[NG][ND], sCol[NG][ND], sQ[NG], sG[ND];
-  __shared__ float sCamG[NJ][3], sL2d[NJ];
+  __shared__ S sAA[ND], sD[NG][ND], sRow[NG][ND], sCol[NG][ND], sG[ND];
+  __shared__ float sQ[NG];
+  __shared__ S sCamG[NJ][3];
+  __shared__ float sL2d[NJ];
   __shared__ int sBest;
   const int b = blockIdx.x, t = threadIdx.x;
   const float invB = 1.0f / (float)a.B;
@@ -353,7 +472,15 @@ __global__ __launch_bounds__(256) void frame_losses_kernel(FrameLossArgs a, DybR
   // --- pose prior: axis-angle of the 23 body joints
   if (t < NJ - 1) {
     QuatFwd f = rot_to_quat(R + (t + 1) * 9);
-    quat_to_aa(f.q, &sAA[t * 3]);
+    float aa[3];
+    quat_to_aa(f.q, aa);
+    if constexpr (IO::dual) {
+      float taa[3];
+      aa_fwd_tan(R + (t + 1) * 9, a.trot + ((size_t)b * NJ + t + 1) * 9, taa);
+      for (int i = 0; i < 3; ++i) sAA[t * 3 + i] = dyb_mk<float>(aa[i], taa[i]);
+    } else {
+      for (int i = 0; i < 3; ++i) sAA[t * 3 + i] = aa[i];
+    }
   }
   __syncthreads();
   for (int i = t; i < NG * ND; i += 256) {
@@ -364,9 +491,9 @@ __global__ __launch_bounds__(256) void frame_losses_kernel(FrameLossArgs a, DybR
   for (int i = t; i < NG * ND; i += 256) {
     int m = i / ND, k = i % ND;
     const float* P = a.prec + (size_t)m * ND * ND;
-    float r = 0.f, c = 0.f;
+    S r = dyb_lit<S>(0.f), c = dyb_lit<S>(0.f);
     for (int j = 0; j < ND; ++j) {
-      float d = sD[m][j];
+      S d = sD[m][j];
       r += P[k * ND + j] * d;
       c += P[j * ND + k] * d;
     }
@@ -376,7 +503,7 @@ __global__ __launch_bounds__(256) void frame_losses_kernel(FrameLossArgs a, DybR
   __syncthreads();
   if (t < NG) {
     float q = 0.f;
-    for (int k = 0; k < ND; ++k) q += sRow[t][k] * sD[t][k];
+    for (int k = 0; k < ND; ++k) q += dyb_val(sRow[t][k]) * dyb_val(sD[t][k]);
     sQ[t] = 0.5f * q - a.logw[t];
   }
   __syncthreads();
@@ -391,54 +518,63 @@ __global__ __launch_bounds__(256) void frame_losses_kernel(FrameLossArgs a, DybR
   if (t < ND) sG[t] = a.wpose * invB * 0.5f * (sRow[mb][t] + sCol[mb][t]);
   __syncthreads();
   if (t < NJ) {
-    float d[9];
+    float d[9], td[9];
     if (t == 0) {
-      for (int k = 0; k < 9; ++k) d[k] = 0.f;
+      for (int k = 0; k < 9; ++k) d[k] = td[k] = 0.f;
+    } else if constexpr (IO::dual) {
+      float g[3], tg[3];
+      for (int i = 0; i < 3; ++i) { g[i] = sG[(t - 1) * 3 + i].v; tg[i] = sG[(t - 1) * 3 + i].t; }
+      aa_bwd(R + t * 9, g, d);
+      aa_bwd_tan(R + t * 9, a.trot + ((size_t)b * NJ + t) * 9, g, tg, td);
     } else {
       aa_bwd(R + t * 9, &sG[(t - 1) * 3], d);
     }
     for (int k = 0; k < 9; ++k) a.drot[((size_t)b * NJ + t) * 9 + k] = d[k];
+    if constexpr (IO::dual)
+      for (int k = 0; k < 9; ++k) a.tdrot[((size_t)b * NJ + t) * 9 + k] = td[k];
   }
 
   // --- 2-D keypoint loss on joints 25..48
-  const float* c = a.cam + (size_t)b * a.ldc;
-  const float den = IMG_RES * c[0] + 1e-9f;
-  const float tz = 2.f * FOCAL / den;
-  for (int i = t; i < NJ49 * 3; i += 256) a.djoints[(size_t)b * NJ49 * 3 + i] = 0.f;
+  const size_t co = (size_t)b * a.ldc;
+  const S c0 = IO::ld(a.cam, a.tcam, co), c1 = IO::ld(a.cam, a.tcam, co + 1), c2 = IO::ld(a.cam, a.tcam, co + 2);
+  const S den = IMG_RES * c0 + 1e-9f;
+  const S tz = 2.f * FOCAL / den;
+  for (int i = t; i < NJ49 * 3; i += 256) IO::st(a.djoints, a.tdjoints, (size_t)b * NJ49 * 3 + i, dyb_lit<S>(0.f));
   __syncthreads();
   if (t < NJ) {
     int j = 25 + t;
-    const float* p = a.joints + ((size_t)b * NJ49 + j) * 3;
+    const size_t p = ((size_t)b * NJ49 + j) * 3;
     const float* k = a.kp + ((size_t)b * NJ49 + j) * 3;
-    float x = p[0] + c[1], y = p[1] + c[2], z = p[2] + tz;
+    S x = IO::ld(a.joints, a.tjoints, p) + c1, y = IO::ld(a.joints, a.tjoints, p + 1) + c2, z = IO::ld(a.joints, a.tjoints, p + 2) + tz;
     const float sc = FOCAL / (IMG_RES * 0.5f);
-    float ex = sc * (x / z) - k[0], ey = sc * (y / z) - k[1];
+    S ex = sc * (x / z) - k[0], ey = sc * (y / z) - k[1];
     float conf = k[2];
     float norm = invB / (float)(NJ * 2);
-    sL2d[t] = conf * (ex * ex + ey * ey) * norm;
-    float gx2 = a.w2d * 2.f * conf * ex * norm, gy2 = a.w2d * 2.f * conf * ey * norm;
-    float gx = gx2 * sc / z, gy = gy2 * sc / z;
-    float gz = -(gx * x + gy * y) / z;
-    float* dj = a.djoints + ((size_t)b * NJ49 + j) * 3;
-    dj[0] = gx; dj[1] = gy; dj[2] = gz;
+    sL2d[t] = conf * (dyb_val(ex) * dyb_val(ex) + dyb_val(ey) * dyb_val(ey)) * norm;
+    S gx2 = a.w2d * 2.f * conf * ex * norm, gy2 = a.w2d * 2.f * conf * ey * norm;
+    S gx = gx2 * sc / z, gy = gy2 * sc / z;
+    S gz = -(gx * x + gy * y) / z;
+    IO::st(a.djoints, a.tdjoints, p, gx); IO::st(a.djoints, a.tdjoints, p + 1, gy); IO::st(a.djoints, a.tdjoints, p + 2, gz);
     sCamG[t][0] = gx; sCamG[t][1] = gy; sCamG[t][2] = gz;
   }
   __syncthreads();
   if (t == 0) {
-    float sx = 0.f, sy = 0.f, sz = 0.f, l2d = 0.f;
+    S sx = dyb_lit<S>(0.f), sy = sx, sz = sx;
+    float l2d = 0.f;
     for (int j = 0; j < NJ; ++j) {
       sx += sCamG[j][0]; sy += sCamG[j][1]; sz += sCamG[j][2];
       l2d += sL2d[j];
     }
-    float* dc = a.dcam + (size_t)b * a.lddc;
-    dc[0] = sz * (-2.f * FOCAL * IMG_RES / (den * den));
-    dc[1] = sx;
-    dc[2] = sy;
-    const float* be = a.shape + (size_t)b * a.lds;
+    const size_t dc = (size_t)b * a.lddc;
+    IO::st(a.dcam, a.tdcam, dc, sz * (-2.f * FOCAL * IMG_RES / (den * den)));
+    IO::st(a.dcam, a.tdcam, dc + 1, sx);
+    IO::st(a.dcam, a.tdcam, dc + 2, sy);
+    const size_t be = (size_t)b * a.lds;
     float lsh = 0.f;
     for (int l = 0; l < 10; ++l) {
-      lsh += be[l] * be[l];
-      a.dshape[(size_t)b * a.ldds + l] = a.wshape * 2.f * be[l] * invB;
+      const S bl = IO::ld(a.shape, a.tshape, be + l);
+      lsh += dyb_val(bl) * dyb_val(bl);
+      IO::st(a.dshape, a.tdshape, (size_t)b * a.ldds + l, a.wshape * 2.f * bl * invB);
     }
     lsh *= invB;
     float lpo = sQ[mb] * invB;
@@ -477,8 +613,40 @@ extern "C" int dyb_frame_losses(const float* rotmat, const float* shape, int lds
   a.drot = drot; a.dshape = dshape; a.dcam = dcam; a.djoints = djoints49;
   a.lds = lds; a.ldc = ldc; a.ldds = ldds; a.lddc = lddc; a.B = B;
   a.w2d = w2d; a.wshape = wshape; a.wpose = wpose;
+  a.trot = a.tshape = a.tcam = a.tjoints = nullptr;
+  a.tdrot = a.tdshape = a.tdcam = a.tdjoints = nullptr;
   const DybRep& Rp = dyb_rep_current();
-  hipLaunchKernelGGL(frame_losses_kernel, dim3(B, 1, Rp.n), dim3(256), 0, st, a, Rp);
+  hipLaunchKernelGGL(frame_losses_kernel<float>, dim3(B, 1, Rp.n), dim3(256), 0, st, a, Rp);
+  DYB_CHECK_LAUNCH();
+  hipLaunchKernelGGL(loss_fold_kernel, dim3(1, 1, Rp.n), dim3(64), 0, st, (const float*)a.parts, losses_out, B, Rp);
+  DYB_CHECK_LAUNCH();
+  return DYB_OK;
+}
+// dyb_frame_losses and, in the same launch, the tangent of its four gradients along (trotmat, tshape, tcam, tjoints49): each t-prefixed
+// array has the shape and leading dimension of its value array.  The quaternion branch of every joint and the mixture component of
+// the pose prior are the ones the value selects.  Single sequence.
+extern "C" int dyb_frame_losses_jvp(const float* rotmat, const float* trotmat, const float* shape, const float* tshape, int lds,
+                                    const float* cam, const float* tcam, int ldc, const float* joints49, const float* tjoints49,
+                                    const float* kp2d, const float* gmm_means, const float* gmm_prec, const float* gmm_logw, float w2d,
+                                    float wshape, float wpose, float* losses_out, float* drot, float* tdrot, float* dshape,
+                                    float* tdshape, int ldds, float* dcam, float* tdcam, int lddc, float* djoints49, float* tdjoints49,
+                                    int B, void* ws, size_t ws_bytes, hipStream_t st) {
+  DYB_REQUIRE(rotmat && trotmat && shape && tshape && cam && tcam && joints49 && tjoints49 && kp2d, DYB_ERR_ARG);
+  DYB_REQUIRE(gmm_means && gmm_prec && gmm_logw && losses_out && drot && tdrot && dshape && tdshape, DYB_ERR_ARG);
+  DYB_REQUIRE(dcam && tdcam && djoints49 && tdjoints49 && ws && B > 0, DYB_ERR_ARG);
+  DYB_REQUIRE(ws_bytes >= (size_t)B * 4 * sizeof(float), DYB_ERR_WORKSPACE);
+  const DybRep& Rp = dyb_rep_current();
+  DYB_REQUIRE(Rp.n == 1, DYB_ERR_UNSUPPORTED);
+  FrameLossArgs a;
+  a.rot = rotmat; a.shape = shape; a.cam = cam; a.joints = joints49; a.kp = kp2d;
+  a.means = gmm_means; a.prec = gmm_prec; a.logw = gmm_logw;
+  a.parts = reinterpret_cast<float*>(ws);
+  a.drot = drot; a.dshape = dshape; a.dcam = dcam; a.djoints = djoints49;
+  a.lds = lds; a.ldc = ldc; a.ldds = ldds; a.lddc = lddc; a.B = B;
+  a.w2d = w2d; a.wshape = wshape; a.wpose = wpose;
+  a.trot = trotmat; a.tshape = tshape; a.tcam = tcam; a.tjoints = tjoints49;
+  a.tdrot = tdrot; a.tdshape = tdshape; a.tdcam = tdcam; a.tdjoints = tdjoints49;
+  hipLaunchKernelGGL(frame_losses_kernel<dualf>, dim3(B, 1, Rp.n), dim3(256), 0, st, a, Rp);
   DYB_CHECK_LAUNCH();
   hipLaunchKernelGGL(loss_fold_kernel, dim3(1, 1, Rp.n), dim3(64), 0, st, (const float*)a.parts, losses_out, B, Rp);
   DYB_CHECK_LAUNCH();

@@ -11,7 +11,10 @@ forward-over-reverse through the network by the library's tangent passes (csrc/h
 
 The head's second derivative is taken as a central difference of ITS analytic gradient along the state tangent - a smooth
 function of 157 inputs per sample evaluated by the same loss / LBS kernels, where a difference quotient is accurate to ~1e-5 -
-while the 50-layer ReLU / GroupNorm backbone, where a difference quotient of the whole network is noisy element-wise, is exact.
+while the 50-layer ReLU / GroupNorm backbone, where a difference quotient of the whole network is noisy element-wise, is exact
+(``head="fd"``, the default).  ``head="closed"`` (``--hvp_head closed``) takes it in closed form instead: one ``dyb_head_hvp`` call
+runs the (value, tangent) instantiation of every head kernel (csrc/dyb_dual.h, csrc/head_hvp.hip) and returns the head's gradient
+and H_head . tstate with no step size; frame-loss levels only (``general_level_hvp`` keeps the difference quotient).
 
 ``frame_level_hvp`` covers levels made of the frame losses only (2-D keypoints + shape prior + pose prior) - the benchmarked
 second-order configuration, checked on the GPU against the reference's second-order golden.  ``general_level_hvp`` covers any
@@ -62,9 +65,46 @@ def _head_grad(lib, smpl, prior, state, kp2d, w2d, wshape, wpose, st):
     return d_state
 
 
-def frame_level_hvp(hmr, smpl, prior, theta, image, kp2d, w2d, wshape, wpose, n_iter: int = 3):
+def head_hvp(lib, smpl, prior, state, tstate, kp2d, w2d, wshape, wpose, st):
+    """(g0, td): the head's gradient at `state` [B][160] (what `_head_grad` returns, bit for bit) and its closed-form second
+    derivative along `tstate`, H_head(state) . tstate, from ONE library call (csrc/head_hvp.hip)."""
+    B = state.shape[0]
+    dev = state.device
+    g0 = torch.empty(B, STATE_LD, dtype=torch.float32, device=dev)
+    td = torch.empty(B, STATE_LD, dtype=torch.float32, device=dev)
+    wsb = int(lib.dyb_head_hvp_workspace_bytes(B))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    check(lib.dyb_head_hvp(smpl._pf, smpl._pi, state.data_ptr(), tstate.data_ptr(), STATE_LD, kp2d.data_ptr(), prior.means.data_ptr(),
+                           prior.precisions.data_ptr(), prior.log_nll_weights.data_ptr(), float(w2d), float(wshape), float(wpose), None,
+                           g0.data_ptr(), td.data_ptr(), STATE_LD, B, ws.data_ptr(), wsb, st), "dyb_head_hvp")
+    return g0, td
+
+
+def head_fd(lib, smpl, prior, state, tstate, kp3, w2d, wshape, wpose, st):
+    """(g0, td) with td the central difference of the head's gradient along `tstate`, step HEAD_FD_REL; kp3: the key points tiled
+    three times (the three evaluation points run as one batch)."""
+    B = state.shape[0]
+    tn = torch.linalg.vector_norm(tstate[:, :157])
+    eps = HEAD_FD_REL * torch.linalg.vector_norm(state[:, :157]) / tn.clamp_min(1e-30)
+    step = torch.zeros_like(state)
+    step[:, :157] = eps * tstate[:, :157]
+    # the head's gradient at the state and at the two difference points as ONE batch of 3 B samples (a third of the launches):
+    # every term of the head is a mean over the batch, so each sample's gradient comes out scaled by 1 / 3
+    g3 = _head_grad(lib, smpl, prior, torch.cat([state, state + step, state - step]).contiguous(), kp3, w2d, wshape, wpose, st) * 3.0
+    g0, gp, gm = g3[:B].contiguous(), g3[B:2 * B], g3[2 * B:]
+    td = ((gp - gm) / (2 * eps)).contiguous()
+    return g0, td
+
+
+HEADS = ("fd", "closed")
+
+
+def frame_level_hvp(hmr, smpl, prior, theta, image, kp2d, w2d, wshape, wpose, n_iter: int = 3, head: str = "fd"):
     """-> callable v -> H v for L(theta) = the frame-loss level (fused_level.level_forward's loss_total) at `theta`
-    (a parameter arena: the learner's current fast weights), on (image, kp2d)."""
+    (a parameter arena: the learner's current fast weights), on (image, kp2d).  head: "fd" - the head's second derivative as a
+    central difference of its gradient (step HEAD_FD_REL); "closed" - in closed form (`head_hvp`)."""
+    if head not in HEADS:
+        raise ValueError(f"head must be one of {HEADS}, got {head!r}")
     lib = _lib.load()
     B, _, H, W = image.shape
     L = get_layout(B, H, W)
@@ -77,7 +117,7 @@ def frame_level_hvp(hmr, smpl, prior, theta, image, kp2d, w2d, wshape, wpose, n_
     from .fused_level import last_forward_acts
     # the level was just evaluated at these weights: its activations are the primal pass (nothing writes to them afterwards)
     level_acts = last_forward_acts(theta, image, init_state, n_iter)
-    kp3 = kp2d.repeat(3, 1, 1)
+    kp3 = kp2d.repeat(3, 1, 1) if head == "fd" else None
 
     def hvp(v):
         v = v.detach().contiguous().float()
@@ -95,15 +135,10 @@ def frame_level_hvp(hmr, smpl, prior, theta, image, kp2d, w2d, wshape, wpose, n_
         state = acts[L.off_state:L.off_state + B * STATE_LD].view(B, STATE_LD)
         off = int(lib.dyb_hmr_hvp_offset_tstate(L.plan))
         tstate = dual[off:off + B * STATE_LD].view(B, STATE_LD)
-        tn = torch.linalg.vector_norm(tstate[:, :157])
-        eps = HEAD_FD_REL * torch.linalg.vector_norm(state[:, :157]) / tn.clamp_min(1e-30)
-        step = torch.zeros_like(state)
-        step[:, :157] = eps * tstate[:, :157]
-        # the head's gradient at the state and at the two difference points as ONE batch of 3 B samples (a third of the launches):
-        # every term of the head is a mean over the batch, so each sample's gradient comes out scaled by 1 / 3
-        g3 = _head_grad(lib, smpl, prior, torch.cat([state, state + step, state - step]).contiguous(), kp3, w2d, wshape, wpose, st) * 3.0
-        g0, gp, gm = g3[:B].contiguous(), g3[B:2 * B], g3[2 * B:]
-        td = ((gp - gm) / (2 * eps)).contiguous()
+        if head == "closed":
+            g0, td = head_hvp(lib, smpl, prior, state, tstate, kp2d, w2d, wshape, wpose, st)
+        else:
+            g0, td = head_fd(lib, smpl, prior, state, tstate, kp3, w2d, wshape, wpose, st)
         hv = torch.zeros(L.n_params, dtype=torch.float32, device=dev)
         check(lib.dyb_hmr_jvp_backward(L.plan, theta.data_ptr(), v.data_ptr(), acts.data_ptr(), dual.data_ptr(), g0.data_ptr(),
                                        td.data_ptr(), n_iter, hv.data_ptr(), ws.data_ptr(), L.ws_bytes, st, aux_stream_of(theta)),

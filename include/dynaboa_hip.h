@@ -276,6 +276,45 @@ int dyb_frame_losses(const float* rotmat, const float* shape, int lds, const flo
                      float wshape, float wpose, float* losses_out, float* drot, float* dshape, int ldds, float* dcam,
                      int lddc, float* djoints49, int B, void* ws, size_t ws_bytes, dyb_stream_t stream);
 
+/* ---- closed-form second derivative of the frame-loss head (--hvp exact --hvp_head closed).
+ * Every *_jvp entry point computes what its sibling computes AND, in the same launches, the directional derivative along the
+ * t-prefixed inputs; a t-prefixed array has the shape and leading dimension of its value array.  The table sweeps (posedirs) are
+ * read once for value and tangent.  The value arrays are the sibling's in the same arithmetic, equal to rounding but not bit for bit
+ * (the compiler contracts the two instantiations differently).  Single sequence only: inside a replica scope they return
+ * DYB_ERR_UNSUPPORTED.
+ *   dyb_rot6d_jvp / dyb_rot6d_bwd_jvp : rot6d -> R along tx6; its gradient along (tx6, tdrotmat)
+ *   dyb_lbs_jvp                       : SMPL forward along (trotmat, tbetas); tsaved (dyb_lbs_saved_floats) = tangents of `saved`
+ *   dyb_frame_losses_jvp              : tangent of the four gradients of dyb_frame_losses, inside the quaternion branch and the
+ *                                       mixture component the value selects
+ *   dyb_lbs_bwd_jvp                   : full tangent of the SMPL backward (its action on tdjoints49 + its own derivative with
+ *                                       respect to pose and shape); ws >= 2 * dyb_lbs_bwd_workspace_bytes(B)
+ *   dyb_head_hvp                      : the whole head on a regressor state [B][ld] (pose6d 144 | shape 10 | cam 3 | pad):
+ *                                       d_state = gradient of w2d * kp2d + wshape * shape prior + wpose * pose prior, bit for bit
+ *                                       what the five calls rot6d_fwd, lbs_fwd, frame_losses, lbs_bwd + head_grad_combine,
+ *                                       rot6d_bwd give (it runs them after the tangent pass);
+ *                                       td_state = H_head(state) . tstate; columns 157.. of both are written as zero (ldd >= 157);
+ *                                       losses4 (may be NULL) as dyb_frame_losses; ws 16-byte aligned. */
+int dyb_rot6d_jvp(const float* x6, const float* tx6, int ldx, float* rotmat, float* trotmat, int B, dyb_stream_t stream);
+int dyb_rot6d_bwd_jvp(const float* x6, const float* tx6, int ldx, const float* drotmat, const float* tdrotmat, float* dx6,
+                      float* tdx6, int lddx, int B, dyb_stream_t stream);
+int dyb_lbs_jvp(const float* const* tables_f, const int* const* tables_i, const float* betas, const float* tbetas, int ldb,
+                const float* rotmat, const float* trotmat, float* verts, float* tverts, float* joints49, float* tjoints49,
+                float* saved, float* tsaved, int B, dyb_stream_t stream);
+int dyb_lbs_bwd_jvp(const float* const* tables_f, const int* const* tables_i, const float* rotmat, const float* trotmat,
+                    const float* saved, const float* tsaved, const float* djoints49, const float* tdjoints49, float* drot,
+                    float* tdrot, float* dbetas, float* tdbetas, int lddb, int B, void* ws, size_t ws_bytes, dyb_stream_t stream);
+int dyb_frame_losses_jvp(const float* rotmat, const float* trotmat, const float* shape, const float* tshape, int lds,
+                         const float* cam, const float* tcam, int ldc, const float* joints49, const float* tjoints49,
+                         const float* kp2d, const float* gmm_means, const float* gmm_prec, const float* gmm_logw, float w2d,
+                         float wshape, float wpose, float* losses_out, float* drot, float* tdrot, float* dshape, float* tdshape,
+                         int ldds, float* dcam, float* tdcam, int lddc, float* djoints49, float* tdjoints49, int B, void* ws,
+                         size_t ws_bytes, dyb_stream_t stream);
+size_t dyb_head_hvp_workspace_bytes(int B);
+int dyb_head_hvp(const float* const* tables_f, const int* const* tables_i, const float* state, const float* tstate, int ld,
+                 const float* kp2d, const float* gmm_means, const float* gmm_prec, const float* gmm_logw, float w2d, float wshape,
+                 float wpose, float* losses4, float* d_state, float* td_state, int ldd, int B, void* ws, size_t ws_bytes,
+                 dyb_stream_t stream);
+
 /* The other terms of the level losses, value + gradient in one launch each (B <= 16): mode 0 mean-teacher consistency
  * (reference base_adaptor.py:320-343: 5 mse(s2d) + 5 mse(s3d) + 0.001 mse(shape) + mse(rotmat) against the teacher's outputs
  * rot2 / shape2 / cam2 / joints2), mode 1 motion (:379-398: confidence-masked mse of the projected-keypoint motion between the
