@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include <vector>
+#include "dyb_switches.h"
 
 #define DYB_OK 0
 #define DYB_ERR_ARG (-1)      // bad pointer / dimension
@@ -210,6 +211,13 @@ struct DybWgradUpdate {
   float* adam_v = nullptr;
   const float* adam_sc = nullptr;
   float b1 = 0.f, b2 = 0.f, eps = 0.f;
+  // does [out, out + count) lie inside the gradient arena of an open scope - then *off = its offset in floats
+  bool claims(const float* out, size_t count, size_t* off) const {
+    const char *lo = reinterpret_cast<const char*>(grads), *o = reinterpret_cast<const char*>(out);
+    if (!grads || o < lo || o + count * sizeof(float) > lo + bytes) return false;
+    *off = (size_t)(o - lo) / sizeof(float);
+    return true;
+  }
 };
 // segment list of a streaming fast-weight launch (optim.hip dyb_fastweight_update_segs): float4 units relative to the arena base
 #define DYB_FW_MAX_SEGS 64
@@ -231,6 +239,8 @@ struct DybConvSyncScope {
 };
 #define DYB_CONV_SYNC_WORDS 16384
 
+// current value of a run-time switch (dyb_switches.h; a relaxed atomic load - igemm_conv.hip)
+int dyb_switch(DybSw which);
 // bf16 matrix-core mode of the calling host thread (igemm_conv.hip)
 bool dyb_bf16_current();
 struct DybBf16Scope {
@@ -265,6 +275,10 @@ int dyb_gn_bwd_reduce_slabs(const float* dout, int nslabs, size_t slab_stride, c
                             const float* y, const float* stats, const float* gamma, const float* beta, float* dm,
                             float* part, int N, int HW, int C, int relu, hipStream_t st, hipEvent_t done);
 int dyb_gn_fwd_chunks(int N, int HW);
+// (norm_pool.hip; public entry points the fused conv entry points of igemm_conv.hip end in)
+extern "C" int dyb_groupnorm_stats(const float* slabs, int nslabs, float* y, float* partials, int N, int HW, int C, hipStream_t st);
+extern "C" int dyb_groupnorm_bwd_reduce(const float* dout, const float* out, const float* y, const float* stats, const float* gamma,
+                                        const float* beta, float* dm, float* part, int N, int HW, int C, int relu, hipStream_t st);
 // data gradient with the GroupNorm backward in its loader that may leave `*nslabs` (>1) un-reduced
 // split-K slabs in `ws` (addend NOT applied then) for the next GroupNorm-backward reduce to fold
 struct GnBwdSrc {
@@ -291,11 +305,6 @@ int dyb_gn_bwd_onepass(const float* din, int nslabs, size_t slab_stride, const f
                        const float* stats, const float* gamma, const float* beta, float* dm, float* dy, float* dgamma, float* dbeta,
                        int HW, int C, int relu, int k, float* part, unsigned* ctr, hipStream_t st);
 int dyb_zero_words(unsigned* p, int n, hipStream_t st);
-int dyb_tp_gn_onepass();
-int dyb_tp_gn_cap();
-int dyb_tp_gn_threads();
-int dyb_tp_gn_poll();
-int dyb_tp_gn_wt();
 int dyb_gn_bwd_apply_dy(const float* dm, const float* y, const float* stats, const float* part, int nch, int ncolb,
                         const float* gamma, float* dy, float* dgamma, float* dbeta, int N, int HW, int C, hipStream_t st);
 int dyb_conv_dgrad_plain_raw(const ConvDesc& d, const float* dy, const float* w, float* dx, const float* addend, void* ws,

@@ -32,8 +32,6 @@ int dyb_conv2d_nhwc_wgrad_gn_n(const float*, const float*, const float*, const f
                                const float*, const float*, int, int, const float*, float*, float*, float*, int, int, int, int,
                                int, int, int, int, int, void*, size_t, hipStream_t);
 size_t dyb_groupnorm_bwd_partial_floats(int, int, int);
-int dyb_groupnorm_bwd_reduce(const float*, const float*, const float*, const float*, const float*, float*, float*, int, int,
-                             int, int, hipStream_t);
 int dyb_conv2d_nhwc_dgrad_gn(const float*, const float*, const float*, const float*, const float*, const float*, float*,
                              const float*, int, int, int, int, int, int, int, int, int, void*, size_t, hipStream_t);
 int dyb_conv2d_nhwc_wgrad_gn(const float*, const float*, const float*, const float*, const float*, const float*, float*,
@@ -698,9 +696,9 @@ static int layer_gn_bwd(HmrPlan& P, int ci, const float* params, const float* ac
   WgradJob j{ci, conv_in, in_prev, dm, 0, 0, nullptr};
   // throughput schedule, one image per replica: the one-pass backward (every tensor read / written once: norm_pool.hip)
   int kop = 0;
-  if (tp && dyb_tp_gn_onepass() > 0) {
-    kop = dyb_gn_onepass_chunks(P.B, c.Ho * c.Wo, c.K, dyb_tp_gn_cap());
-    if (kop > 1 && (dyb_tp_gn_onepass() < 2 || dyb_gn_onepass_part_floats(kop, c.K) > dyb_groupnorm_bwd_partial_floats(P.B, c.Ho * c.Wo, c.K)))
+  if (tp && dyb_switch(DYB_SW_tp_gn_onepass) > 0) {
+    kop = dyb_gn_onepass_chunks(P.B, c.Ho * c.Wo, c.K, dyb_switch(DYB_SW_tp_gn_cap));
+    if (kop > 1 && (dyb_switch(DYB_SW_tp_gn_onepass) < 2 || dyb_gn_onepass_part_floats(kop, c.K) > dyb_groupnorm_bwd_partial_floats(P.B, c.Ho * c.Wo, c.K)))
       kop = 0;
   }
   if (kop > 0) {

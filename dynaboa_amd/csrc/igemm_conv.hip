@@ -67,7 +67,7 @@ struct IgemmArgs {
   int wt;                // throughput form: cache policy of the result stores ("tp_wt": 0 plain, 1 sc1 write-through, 2 nt, 3 sc0 sc1)
   int cls_tile0[4];      // throughput data gradient: first tile (grid x) of each phase class (stride 2)
   int compact;           // throughput data gradient of a 1x1 stride-2 conv: only the one class that has a tap is computed, rows written
-                         // COMPACT (class-local index) into slabs of slab_rows rows; a scatter fold places them (run_igemm_tp)
+                         // COMPACT (class-local index) into slabs of slab_rows rows; a scatter fold places them (issue_conv)
   int slab_rows;         // rows of one split-K slab (M unless compact)
   unsigned long long* probe;   // throughput form: per-wave phase clocks (dyb_conv_probe_set), normally NULL
   const float* A2;       // operand PAIR (latency form, no fused loaders): out = A (x) B + A2 (x) B2 as ONE K loop - K-tiles [0, ktiles1)
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(256) void igemm_mfma_kernel(IgemmArgs g, GnBwdFuse 
     if (n0 + d_q < g.Ncols) wg_gamma = *reinterpret_cast<const float4*>(f.gamma + n0 + d_q);
   }
 
-  // the second operand pair of a paired launch (uniform per K-step; the fused loaders never see one: run_igemm)
+  // the second operand pair of a paired launch (uniform per K-step; the fused loaders never see one: plan_conv)
   auto load_a = [&](int kt, int h, Frag& o) {
     const bool second = kt >= g.ktiles1;
     const float* __restrict__ Ap = second ? g.A2 : g.A;
@@ -1259,17 +1259,16 @@ DybRepScope::~DybRepScope() { t_rep = saved; }
 // leave slabs as before.  The words must be zero when the first launch uses them; every launch leaves them zero.  One word per
 // (replica slot of the launch, tile): the region is NOT replicated - a pointer into replica 0's workspace serves every replica.
 static thread_local DybConvSync t_conv_sync = {nullptr, 0};
-// Weight-update scope of the calling thread (round 6, "fuse_fast"): while one is open, a throughput-form WEIGHT GRADIENT that (a) would
-// write its result into [grads, grads + bytes), (b) runs unsplit (nsplit == 1: the accumulators hold the finished gradient tile) leaves
-// p_next[off] = p_cur[off] - lr * g instead of g - the fast-weight step of learn2learn's MAML.adapt (p' = p - lr * dL/dp; call sites
-// reference dynaboa_benchmark.py:136,140) fused into the epilogue: one read of the current weights and one write of the new ones instead
-// of writing g and a streaming pass reading p and g and writing p'.  The span is appended to `spans` so that the caller's streaming
-// pass can leave it out.  First order only (the inner gradients have no other reader).
+// Weight-update scope of the calling thread ("fuse_fast" / "fuse_adam"): while one is open, a WEIGHT GRADIENT that would write its result into
+// [grads, grads + bytes) leaves p_next[off] = p_cur[off] - lr * g instead of g - the fast-weight step of learn2learn's MAML.adapt (p' = p - lr *
+// dL/dp; call sites reference dynaboa_benchmark.py:136,140) - or Adam-updated weights and moments: one read of the current weights and one write
+// of the new ones instead of writing g and a streaming pass reading p and g and writing p'.  The span is appended to `spans` so that the caller's
+// streaming pass can leave it out.  First order only (the inner gradients have no other reader).  Which launch forms take it: plan_weight_update.
 static thread_local DybWgradUpdate t_wupd = {};
 DybWgradUpdateScope::DybWgradUpdateScope(const DybWgradUpdate& u) : saved(t_wupd) { t_wupd = u; }
 DybWgradUpdateScope::~DybWgradUpdateScope() { t_wupd = saved; }
 const DybWgradUpdate& dyb_wgrad_update_current() { return t_wupd; }
-static std::vector<DybSpan> t_debug_spans;
+static thread_local std::vector<DybSpan> t_debug_spans;
 // tests / lab: a scope for the calling thread's plain weight-gradient calls until reset with grads = NULL; dyb_debug_wgrad_update_spans
 // reports how many launches took the fused form since the scope was set
 extern "C" int dyb_debug_set_wgrad_update(const float* grads, size_t bytes, const float* p_cur, float* p_next, float lr) {
@@ -1298,85 +1297,29 @@ extern "C" int dyb_debug_set_conv_sync(unsigned* ctr, int nwords) {
   return DYB_OK;
 }
 
-// ---- run-time switches ------------------------------------------------------------------------------------
-// Read from the environment ONCE (first use), never on the dispatch path; dyb_set_option changes one afterwards
-// (tests / A-B runs).  Names: "k4" (single-launch 1x1 forward + statistics), "k4_bwd" (1x1 data gradient carries the
-// producer's GroupNorm-backward reduce), "k4_batch" (both at batch > 1), "k4_maxc" (their channel limit), "rep_split"
-// (replica-aware policy: split-K depth chosen for the replica-multiplied grid and, from "tp_min" replicas per launch on,
-// the throughput schedule - dy materialised once per layer, plain gradient convolutions, no single-launch 1x1 kernels),
-// "tp_kernel" (throughput schedule runs igemm_tp_kernel: 128x128-class tiles, 2 = its software-pipelined loop (default), 1 = round 2's
-// phase-separated loop; 0 = the 64x64 kernel), "tp_grid" (workgroups
-// its split-K aims for), "tp_batch_min" (8; > 0: the throughput schedule also for single-sequence launches of at least that batch:
-// +13.5 % at batch 16 in BENCH_r02, and the schedule the bf16 form of igemm_tp_kernel needs), "tp_gn_wgs" (workgroups a GroupNorm launch aims for over all replicas
-// under the throughput policy: their chunk counts are otherwise sized for one sequence and the launches dispatch-bound), "bf16" (bf16 matrix cores for direct calls of the conv entry points).
+// ---- run-time switches: storage, environment read and name lookup generated from dyb_switches.h -------------------
 struct DybSwitches {
-  std::atomic<int> k4, k4_bwd, k4_batch, k4_maxc, rep_split, bf16, tp_min, tp_kernel, tp_grid, tp_xcd, tp_batch_min, tp_gn_wgs, tp_occ, tp_gn_onepass,
-      tp_gn_cap, tp_gn_threads, tp_gn_fuse_stats, tp_gn_poll, tp_fwd_nosplit2, pair, tp_wt, tp_fold, lat_fold, stat_folds, tp_gn_wt, tp_stem;
+  std::atomic<int> v[DYB_SW_COUNT];
   DybSwitches() {
-    auto env = [](const char* n, int d) { const char* v = getenv(n); return v ? atoi(v) : d; };
-    k4 = env("DYB_K4", 1);
-    k4_bwd = env("DYB_K4_BWD", 1);
-    k4_batch = env("DYB_K4_BATCH", 1);
-    k4_maxc = env("DYB_K4_MAXC", 1024);
-    rep_split = env("DYB_REP_SPLIT", 0);
-    bf16 = 0;
-    tp_min = env("DYB_TP_MIN", 8);
-    tp_kernel = env("DYB_TP_KERNEL", 2);
-    tp_grid = env("DYB_TP_GRID", 512);
-    tp_xcd = env("DYB_TP_XCD", 1);
-    tp_batch_min = env("DYB_TP_BATCH_MIN", 8);       // measured crossover (r05 s17): batch 6: 257.7 | 251.0, 8: 280.8 | 294.9, 12: 304.0 | 366.6, 16: 320.9 | 418.6 frames/s latency | throughput
-    tp_gn_wgs = env("DYB_TP_GN_WGS", 1024);
-    tp_occ = env("DYB_TP_OCC", 0);
-    tp_gn_onepass = env("DYB_TP_GN_ONEPASS", 2);
-    tp_gn_cap = env("DYB_TP_GN_CAP", 0);
-    tp_gn_threads = env("DYB_TP_GN_THREADS", 1024);
-    tp_gn_fuse_stats = env("DYB_TP_GN_FUSE_STATS", 1);
-    tp_gn_poll = env("DYB_TP_GN_POLL", 8);
-    tp_fwd_nosplit2 = env("DYB_TP_FWD_NOSPLIT2", 1);
-    pair = env("DYB_CONV_PAIR", 1);
-    tp_wt = env("DYB_TP_WT", 1);
-    tp_stem = env("DYB_TP_STEM", 1);
-    tp_fold = env("DYB_TP_FOLD", 0);       // measured (r05 s3): 32 sequences 461 vs 463 frames/s off, 16: 362 vs 376 - the folding workgroups are a tail
-    lat_fold = env("DYB_LAT_FOLD", 1);
-    stat_folds = 0;
-    tp_gn_wt = env("DYB_TP_GN_WT", 0);
+    auto env = [](const char* n, int d) { const char* e = n ? getenv(n) : nullptr; return e ? atoi(e) : d; };
+#define DYB_SW_INIT_(id, name, envname, dflt, doc) v[DYB_SW_##id] = env(envname, dflt);
+    DYB_SWITCH_TABLE(DYB_SW_INIT_)
+#undef DYB_SW_INIT_
   }
 };
 static DybSwitches& switches() {
   static DybSwitches* s = new DybSwitches();
   return *s;
 }
+int dyb_switch(DybSw which) { return switches().v[which].load(std::memory_order_relaxed); }
 // bf16 mode: the engine's scope for this thread, or the process-wide "bf16" switch (direct calls of the conv entry points)
-bool dyb_bf16_current() { return t_bf16 || switches().bf16.load(std::memory_order_relaxed) != 0; }
+bool dyb_bf16_current() { return t_bf16 || dyb_switch(DYB_SW_bf16) != 0; }
 static std::atomic<int>* find_switch(const char* name) {
   if (!name) return nullptr;
-  DybSwitches& s = switches();
-  if (!strcmp(name, "k4")) return &s.k4;
-  if (!strcmp(name, "k4_bwd")) return &s.k4_bwd;
-  if (!strcmp(name, "k4_batch")) return &s.k4_batch;
-  if (!strcmp(name, "k4_maxc")) return &s.k4_maxc;
-  if (!strcmp(name, "rep_split")) return &s.rep_split;
-  if (!strcmp(name, "bf16")) return &s.bf16;
-  if (!strcmp(name, "tp_min")) return &s.tp_min;
-  if (!strcmp(name, "tp_kernel")) return &s.tp_kernel;
-  if (!strcmp(name, "tp_grid")) return &s.tp_grid;
-  if (!strcmp(name, "tp_xcd")) return &s.tp_xcd;
-  if (!strcmp(name, "tp_batch_min")) return &s.tp_batch_min;
-  if (!strcmp(name, "tp_gn_wgs")) return &s.tp_gn_wgs;
-  if (!strcmp(name, "tp_occ")) return &s.tp_occ;
-  if (!strcmp(name, "tp_gn_onepass")) return &s.tp_gn_onepass;
-  if (!strcmp(name, "tp_gn_cap")) return &s.tp_gn_cap;
-  if (!strcmp(name, "tp_gn_threads")) return &s.tp_gn_threads;
-  if (!strcmp(name, "tp_gn_fuse_stats")) return &s.tp_gn_fuse_stats;
-  if (!strcmp(name, "tp_gn_poll")) return &s.tp_gn_poll;
-  if (!strcmp(name, "tp_fwd_nosplit2")) return &s.tp_fwd_nosplit2;
-  if (!strcmp(name, "conv_pair")) return &s.pair;
-  if (!strcmp(name, "tp_wt")) return &s.tp_wt;
-  if (!strcmp(name, "tp_stem")) return &s.tp_stem;
-  if (!strcmp(name, "tp_fold")) return &s.tp_fold;
-  if (!strcmp(name, "lat_fold")) return &s.lat_fold;
-  if (!strcmp(name, "tp_gn_wt")) return &s.tp_gn_wt;
-  if (!strcmp(name, "stat_folds")) return &s.stat_folds;      // (a counter, not a switch: conv launches that folded their split in-kernel)
+#define DYB_SW_FIND_(id, sname, envname, dflt, doc) \
+  if (!strcmp(name, sname)) return &switches().v[DYB_SW_##id];
+  DYB_SWITCH_TABLE(DYB_SW_FIND_)
+#undef DYB_SW_FIND_
   return nullptr;
 }
 extern "C" int dyb_set_option(const char* name, int value) {
@@ -1402,7 +1345,7 @@ static int choose_split(const IgemmArgs& g, size_t ws_floats, int mode, bool raw
   // rep_split = 1: a launch covering n sequence replicas already has n x the workgroups, so the grid cap counts them and
   // the K loop is split less (fewer slabs to write and fold).  Off by default: the split depth fixes the summation order,
   // and with it off a replica's results are bit-identical to the same sequence running alone.
-  if (switches().rep_split.load(std::memory_order_relaxed)) tiles *= dyb_rep_current().n;
+  if (dyb_switch(DYB_SW_rep_split)) tiles *= dyb_rep_current().n;
   int maxs = g.ktiles / (min_steps > 0 ? min_steps : 1);
   if (maxs < 1) maxs = 1;
   int gridcap = grid_cap / tiles;
@@ -1612,30 +1555,146 @@ __global__ __launch_bounds__(256) void fold_scatter_s2_kernel(const float4* __re
 
 #include "igemm_tp.inc"
 
-// The throughput form (igemm_tp.inc) of one mode; same contract as run_igemm below.
-static bool tp_eligible(int mode, const ConvDesc& d, const GnBwdFuse* fuse) {
-  if (fuse || !dyb_throughput_mode(d.N)) return false;
-  const int tpk_ = switches().tp_kernel.load(std::memory_order_relaxed);
-  if (!tpk_) return false;
-  if (dyb_bf16_current() && (tpk_ < 2 || (mode == MODE_WGRAD && TPK / conv_out_dim(d.W, d.S, d.stride, d.pad) >= conv_out_dim(d.H, d.R, d.stride, d.pad))))
-    return false;                                  // the bf16 form exists for the pipelined loop only
+// ---- one convolution launch: a call, a plan, an issuer ------------------------------------------------------------------
+// ConvCall is what an entry point asks for, ConvPlan everything the launch needs and everything it will report.  plan_conv DECIDES and
+// has no side effects: it reads the switches and the calling thread's scopes (replica set, conv-sync region, weight-update scope,
+// bf16, probe) and writes only the plan; every refusal lives there.  issue_conv DOES: timing pair, launch, fold / scatter launch, and
+// only then the reports (span, stat_folds, *nslabs, *stats_nrec) - so nothing is reported for a launch that never happened.
+struct ConvCall {
+  int mode;
+  ConvDesc d;
+  const float *A, *B;               // fwd: x, w      dgrad: dy, w     wgrad: x, dy
+  const float *A2, *B2;             // optional second operand pair: one K loop over both (latency form, no fused loaders: dyb_conv_pair_supported)
+  float* out;
+  const float* addend;
+  void* ws;
+  size_t ws_bytes;
+  // non-null: where the policy picks nsplit > 1 the slabs may be left in the workspace un-reduced (addend NOT applied) and *nslabs =
+  // their number - the caller folds them, e.g. inside the GroupNorm statistics kernel; *nslabs = 1: the result is in `out`
+  int* nslabs;
+  const GnBwdFuse* fuse;            // GroupNorm backward of the conv's output formed in the loader
+  const GnFwdFuse* nfuse;           // producer GroupNorm(+ReLU) applied in the loader
+  // forward only: where the GroupNorm statistics of the output may leave with the tiles (one image, unsplit or folded in kernel, at most
+  // min(Ho*Wo, 256) records - what a layer's partial slot holds); *stats_nrec = records written, 0 = none
+  float* stats_part;
+  int* stats_nrec;
+};
+// the part every call has; everything optional is set by field name
+static ConvCall conv_call(int mode, const ConvDesc& d, const float* A, const float* B, float* out, void* ws, size_t ws_bytes) {
+  ConvCall c{};
+  c.mode = mode; c.d = d; c.A = A; c.B = B; c.out = out; c.ws = ws; c.ws_bytes = ws_bytes;
+  return c;
+}
+enum { FAM_LATENCY, FAM_THROUGHPUT, FAM_STEM };        // igemm_mfma_kernel | igemm_tp_kernel | its Cin = 4 loader form
+// how the result leaves: straight from the accumulators | folded by the last workgroup to arrive on a tile's counter | slabs + a fold
+// launch | compact slabs + the scatter fold (1x1 stride-2 data gradient) | slabs left for the caller's next kernel
+enum { EXIT_DIRECT, EXIT_KERNEL_FOLD, EXIT_FOLD_LAUNCH, EXIT_SCATTER, EXIT_RAW_SLABS };
+enum { UPD_NONE, UPD_FAST, UPD_ADAM };
+struct ConvPlan {
+  int family, form, pipe;          // throughput: tile form 0 = 128x128, 1 = 64x256, 2 = 256x64; loop form 0 phase-separated, 1 / 2 pipelined
+  bool bf;
+  IgemmArgs g;
+  GnBwdFuse f;                     // the call's fused loaders by value (zero: none)
+  GnFwdFuse nf;
+  dim3 grid;
+  unsigned lds;                    // dynamic LDS ("tp_occ")
+  int exit;
+  size_t slab_floats;              // one split-K slab
+  float* fold_out;                 // EXIT_FOLD_LAUNCH: out = fold_addend + fold_scale * sum of the slabs (no addend: the plain sum)
+  const float* fold_addend;
+  float fold_scale;
+  int upd;                         // weight-update claim: the launch leaves updated weights instead of the gradient [upd_off, upd_off + upd_n)
+  size_t upd_off, upd_n;           // of the scope's arena (floats)
+  int stats_nrec;
+  char tag;                        // timing table: f / d / w latency form, t / u / v throughput form
+  int timing_upd;                  // byte accounting of the timing scope: 1 fast-weight, 2 Adam epilogue
+};
+
+// throughput form (igemm_tp.inc) or latency form - the first step of planning
+static bool tp_eligible(int mode, const ConvDesc& d, int Ho, int Wo, int tpk, bool bf, bool gn_bwd_fused) {
+  if (gn_bwd_fused || !dyb_throughput_mode(d.N) || !tpk) return false;
+  if (bf && (tpk < 2 || (mode == MODE_WGRAD && TPK / Wo >= Ho))) return false;       // the bf16 form exists for the pipelined loop only
   // buffer addressing: 32-bit byte offsets, one mask bit per filter tap
   const size_t lim = 0x7fffffffu / sizeof(float);
-  const int Ho = conv_out_dim(d.H, d.R, d.stride, d.pad), Wo = conv_out_dim(d.W, d.S, d.stride, d.pad);
   if ((size_t)d.N * d.H * d.W * d.C + (size_t)d.W * d.C * 8 >= lim || (size_t)d.N * Ho * Wo * d.K + (size_t)Wo * d.K * 8 >= lim ||
       (size_t)d.R * d.S * d.C * d.K >= lim)
     return false;
   // the stem (Cin = 4): its own loader form of the pipelined forward kernel ("C4", igemm_tp.inc; switch tp_stem)
-  if (mode == MODE_FWD && d.C == 4)
-    return tpk_ >= 2 && d.K <= 64 && d.S >= TPK / 4 && !dyb_bf16_current() && switches().tp_stem.load(std::memory_order_relaxed) != 0;
+  if (mode == MODE_FWD && d.C == 4) return tpk >= 2 && d.K <= 64 && d.S >= TPK / 4 && !bf && dyb_switch(DYB_SW_tp_stem) != 0;
   if (mode == MODE_FWD) return d.C % TPK == 0 && d.R * d.S <= 32;
   if (mode == MODE_DGRAD) return d.K % TPK == 0 && d.R * d.S <= 32;
   return true;
 }
-// stats_part / stats_nrec (forward only): where the GroupNorm statistics of the output may leave with the tiles ("tp_gn_fuse_stats":
-// one image, nsplit == 1, at most min(Ho*Wo, 256) records - what a layer's partial slot holds); *stats_nrec = records written, 0 = none
-static int run_igemm_tp(int mode, const ConvDesc& d, IgemmArgs g, float* out, const float* addend, void* ws, size_t ws_bytes,
-                        int* raw_slabs_out, hipStream_t st, const GnFwdFuse* nfuse, float* stats_part = nullptr, int* stats_nrec = nullptr) {
+
+// ---- what the two planners share ----
+// split finalisation: clamp to the workspace, then drop empty tail splits
+static void finish_split(IgemmArgs& g, int s, size_t slab_floats, size_t ws_floats) {
+  while (s > 1 && (size_t)s * slab_floats > ws_floats) --s;
+  g.tiles_per_split = dyb_cdiv(g.ktiles, s);
+  g.nsplit = dyb_cdiv(g.ktiles, g.tiles_per_split);
+}
+// In-kernel split-K fold: the kernel form has one and its switch is on (`kernel_folds`), a counter region is in scope with one word per
+// (replica slot of the launch, tile) - and not where the caller's next kernel folds the slabs while it reads them anyway (a gradient
+// handed on as raw slabs)
+static bool fold_in_kernel(const ConvCall& c, const ConvPlan& p, bool kernel_folds) {
+  return p.g.nsplit > 1 && kernel_folds && t_conv_sync.ctr &&
+         (long)p.grid.x * p.grid.y * dyb_rep_current().n <= (long)t_conv_sync.nwords && !(c.nslabs && c.mode != MODE_FWD);
+}
+// GroupNorm statistics of a forward's output with the tiles: the caller has a slot, one image, and `records` fit what a layer's
+// partial slot holds (the planners add their kernel's own limits)
+static bool stats_fit(const ConvCall& c, const IgemmArgs& g, int records) {
+  return c.mode == MODE_FWD && c.stats_part && c.stats_nrec && c.d.N == 1 && c.d.K >= 64 && records <= std::min(g.Ho * g.Wo, 256);
+}
+// the kernel's and the fold launch's destinations for the exit the planner chose
+static void route_result(const ConvCall& c, ConvPlan& p) {
+  IgemmArgs& g = p.g;
+  const bool direct = p.exit == EXIT_DIRECT;
+  g.out = direct ? c.out : reinterpret_cast<float*>(c.ws);
+  g.addend = direct ? c.addend : nullptr;
+  g.out_scale = 1.f;
+  if (p.exit == EXIT_KERNEL_FOLD) { g.fold_out = c.out; g.fold_addend = c.addend; g.fold_ctr = t_conv_sync.ctr; }
+  p.fold_out = c.out; p.fold_addend = c.addend; p.fold_scale = 1.f;
+}
+// Weight-update claim (DybWgradUpdateScope above): a WEIGHT GRADIENT whose result would land inside the scope's gradient arena leaves
+// p_next = p_cur - lr * g (or Adam-updated weights and moments) instead of g, from wherever the finished gradient tile is formed.  Who
+// may take it, in one place:
+static void plan_weight_update(const ConvCall& c, ConvPlan& p) {
+  const DybWgradUpdate& u = t_wupd;
+  IgemmArgs& g = p.g;
+  const size_t n = (size_t)g.M * g.Ncols;
+  size_t off = 0;
+  if (c.mode != MODE_WGRAD || c.addend || !u.claims(c.out, n, &off)) return;
+  const bool adam = u.adam_m != nullptr;
+  bool ok;
+  if (p.family == FAM_LATENCY)
+    // latency form (one sequence): the fast-weight step through any of its three exits - unsplit, folded in kernel, fold launch; fp32
+    // form, one operand pair, the result not handed on as raw slabs.  No Adam epilogue in this kernel.
+    ok = !adam && !p.bf && !c.A2 && !c.nslabs;
+  else if (p.exit == EXIT_DIRECT)
+    // throughput form, unsplit (the accumulators hold the finished tile): the epilogue writes the fast-weight step, or applies Adam -
+    // which only the pipelined loop forms carry: with pipe == 0 an Adam scope is declined, the plain gradient goes to the gradient
+    // arena and the streaming Adam pass covers it, as no span is reported
+    ok = !adam || p.pipe != 0;
+  else
+    // throughput form, split: the fast-weight step rides in the fold launch - not Adam, not the in-kernel fold (declined wherever
+    // "tp_fold" asks for one for weight gradients, whether or not a counter region is in scope)
+    ok = !adam && p.exit == EXIT_FOLD_LAUNCH && !((dyb_switch(DYB_SW_tp_fold) >> MODE_WGRAD) & 1);
+  if (!ok) return;
+  p.upd = adam ? UPD_ADAM : UPD_FAST; p.upd_off = off; p.upd_n = n;
+  if (p.exit == EXIT_DIRECT) { g.out = u.p_next + off; g.addend = u.p_cur + off; g.out_scale = -u.lr; }
+  else if (p.exit == EXIT_KERNEL_FOLD) { g.fold_out = u.p_next + off; g.fold_addend = u.p_cur + off; g.out_scale = -u.lr; }
+  else { p.fold_out = u.p_next + off; p.fold_addend = u.p_cur + off; p.fold_scale = -u.lr; }
+  if (adam) {
+    g.adam_m = u.adam_m + off; g.adam_v = u.adam_v + off; g.adam_sc = u.adam_sc;
+    g.adam_b1 = u.b1; g.adam_b2 = u.b2; g.adam_eps = u.eps;
+    g.out_scale = 0.f;                  // (only marks the launch as a fused update for the byte accounting)
+  }
+}
+
+static int plan_throughput(const ConvCall& c, ConvPlan& p, int tpk) {
+  const ConvDesc& d = c.d;
+  const int mode = c.mode;
+  IgemmArgs& g = p.g;
   const DybRep& R = dyb_rep_current();
   // tile form: 128x128, or one 64-slab along the short side.  A stride-2 data gradient enumerates its rows by phase class
   // ((h+pad)&1, (w+pad)&1) - tiles never mix classes, each class loops over its own taps - so the row count that matters is
@@ -1644,29 +1703,29 @@ static int run_igemm_tp(int mode, const ConvDesc& d, IgemmArgs g, float* out, co
   const int rows_form = classes ? d.N * ((d.H + 1) >> 1) * ((d.W + 1) >> 1) : g.M;
   const int form = g.Ncols <= 64 ? 2 : (rows_form <= 64 ? 1 : 0);
   const int TM = form == 0 ? 128 : form == 1 ? 64 : 256, TN = form == 0 ? 128 : form == 1 ? 256 : 64;
+  p.family = (mode == MODE_FWD && d.C == 4) ? FAM_STEM : FAM_THROUGHPUT;
+  p.form = form;
   g.ktiles = dyb_cdiv(g.Kdim, TPK);
-  g.xcd = switches().tp_xcd.load(std::memory_order_relaxed);
-  g.wt = switches().tp_wt.load(std::memory_order_relaxed);
+  g.xcd = dyb_switch(DYB_SW_tp_xcd);
+  g.wt = dyb_switch(DYB_SW_tp_wt);
   int mtiles = dyb_cdiv(g.M, TM), work_mtiles = mtiles;
-  g.cls_tile0[0] = g.cls_tile0[1] = g.cls_tile0[2] = g.cls_tile0[3] = 0;
   if (classes) {
     mtiles = work_mtiles = 0;
-    for (int c = 0; c < 4; ++c) {
-      const int h0 = ((c >> 1) + d.pad) & 1, w0 = ((c & 1) + d.pad) & 1;
+    for (int cl = 0; cl < 4; ++cl) {
+      const int h0 = ((cl >> 1) + d.pad) & 1, w0 = ((cl & 1) + d.pad) & 1;
       const int rows = d.N * ((d.H - h0 + 1) >> 1) * ((d.W - w0 + 1) >> 1);
       DYB_REQUIRE(rows < (1 << 20) && d.H <= 1024 && d.W <= 1024, DYB_ERR_UNSUPPORTED);
-      g.cls_tile0[c] = mtiles;
+      g.cls_tile0[cl] = mtiles;
       mtiles += dyb_cdiv(rows, TM);
-      const bool has_taps = ((d.R - (c >> 1) + 1) >> 1) > 0 && ((d.S - (c & 1) + 1) >> 1) > 0;
+      const bool has_taps = ((d.R - (cl >> 1) + 1) >> 1) > 0 && ((d.S - (cl & 1) + 1) >> 1) > 0;
       if (has_taps) work_mtiles += dyb_cdiv(rows, TM);                 // a class without taps only writes zeros (+ addend)
     }
     g.ktiles = ((d.R + 1) >> 1) * ((d.S + 1) >> 1) * (d.K / TPK);      // the deepest class (split policy)
   }
   // 1x1 stride-2 (the downsample convs): one class has the tap, three have none - compute that class alone into compact slabs
-  g.compact = 0;
   g.slab_rows = g.M;
   const int Hc = (d.H + 1) >> 1, Wc = (d.W + 1) >> 1;
-  if (classes && d.R == 1 && d.S == 1 && d.pad == 0 && ws && (size_t)d.N * Hc * Wc * g.Ncols * sizeof(float) <= ws_bytes) {
+  if (classes && d.R == 1 && d.S == 1 && d.pad == 0 && c.ws && (size_t)d.N * Hc * Wc * g.Ncols * sizeof(float) <= c.ws_bytes) {
     g.compact = 1;
     g.slab_rows = d.N * Hc * Wc;
     mtiles = work_mtiles = dyb_cdiv(g.slab_rows, TM);
@@ -1674,274 +1733,189 @@ static int run_igemm_tp(int mode, const ConvDesc& d, IgemmArgs g, float* out, co
     g.cls_tile0[1] = g.cls_tile0[2] = g.cls_tile0[3] = 0x7fffffff;
   }
   const long tiles = (long)work_mtiles * dyb_cdiv(g.Ncols, TN) * R.n;
-  int s = (int)(switches().tp_grid.load(std::memory_order_relaxed) / tiles);
+  int s = (int)(dyb_switch(DYB_SW_tp_grid) / tiles);
   const int maxs = g.ktiles / 4 > 0 ? g.ktiles / 4 : 1;                 // every split keeps >= 4 K-steps
   if (s > maxs) s = maxs;
   if (s < 1) s = 1;
   // forward, one image: an unsplit launch leaves the output's GroupNorm statistics with its tiles (no statistics launch, no slabs to
   // write and fold) - worth more than the second workgroup per CU a split of two would buy ("tp_fwd_nosplit2")
-  bool stats_fusable = false;
-  int stats_records = 0;
-  if (mode == MODE_FWD && stats_part && stats_nrec && d.N == 1 && d.K >= 64 && d.K <= 2048 &&
-      switches().tp_gn_fuse_stats.load(std::memory_order_relaxed)) {
-    stats_records = mtiles * dyb_cdiv(g.Ncols, TN) * (TM / 64) * (TN / 64);
-    const int HWo = g.Ho * g.Wo;
-    stats_fusable = stats_records <= (HWo < 256 ? HWo : 256);
-  }
-  if (stats_fusable && s == 2 && switches().tp_fwd_nosplit2.load(std::memory_order_relaxed)) s = 1;
-  const size_t per = (size_t)g.slab_rows * g.Ncols, ws_floats = ws ? ws_bytes / sizeof(float) : 0;
+  const int stats_records = mtiles * dyb_cdiv(g.Ncols, TN) * (TM / 64) * (TN / 64);
+  const bool stats_fusable = stats_fit(c, g, stats_records) && d.K <= 2048 && dyb_switch(DYB_SW_tp_gn_fuse_stats);
+  if (stats_fusable && s == 2 && dyb_switch(DYB_SW_tp_fwd_nosplit2)) s = 1;
+  p.slab_floats = (size_t)g.slab_rows * g.Ncols;
   // the result tiles leave through 32-bit byte offsets into a buffer resource clamped to 2^31 - 1 bytes: a larger slab would alias TP_OOB
-  // and its stores would be dropped silently (ADVICE r5)
-  DYB_REQUIRE(per * sizeof(float) < 0x7fffffffull, DYB_ERR_UNSUPPORTED);
-  while (s > 1 && (size_t)s * per > ws_floats) --s;
-  g.nsplit = s;
-  g.tiles_per_split = dyb_cdiv(g.ktiles, g.nsplit);
-  g.nsplit = dyb_cdiv(g.ktiles, g.tiles_per_split);
-  if (raw_slabs_out) *raw_slabs_out = 1;
-  const bool split = g.nsplit > 1;
-  g.out = (split || g.compact) ? reinterpret_cast<float*>(ws) : out;          // (compact: always through the scatter fold)
-  g.addend = (split || g.compact) ? nullptr : addend;
-  g.out_scale = 1.f;
-  dim3 grid(mtiles, dyb_cdiv(g.Ncols, TN), g.nsplit * R.n);
-  g.probe = probe_for(mode, d, (long)grid.x * grid.y * grid.z);
+  // and its stores would be dropped silently
+  DYB_REQUIRE(p.slab_floats * sizeof(float) < 0x7fffffffull, DYB_ERR_UNSUPPORTED);
+  finish_split(g, s, p.slab_floats, c.ws ? c.ws_bytes / sizeof(float) : 0);
+  p.grid = dim3(mtiles, dyb_cdiv(g.Ncols, TN), g.nsplit * R.n);
+  g.probe = probe_for(mode, d, (long)p.grid.x * p.grid.y * p.grid.z);
   // "tp_kernel" 2 (default): the software-pipelined loop (PIPE 1), 3: the same with two K-steps of loads in flight (PIPE 2);
-  // 1: round 2's phase-separated loop (also what the phase probe and
-  // weight gradients over maps too small for the branch-free pixel walk use)
-  const int tpk = switches().tp_kernel.load(std::memory_order_relaxed);
-  const int pipe = (tpk >= 2 && !g.probe && !(mode == MODE_WGRAD && TPK / g.Wo >= g.Ho)) ? (tpk >= 3 ? 2 : 1) : 0;
-  // (a SPLIT weight gradient whose slabs the fold launch below adds: the fast-weight step rides in that launch - not Adam, not the in-kernel fold)
-  const float* red_addend = addend;
-  float* red_out = out;
-  float red_scale = 1.f;
-  if (mode == MODE_WGRAD && t_wupd.grads && !t_wupd.adam_m && split && !g.compact && !addend && !raw_slabs_out &&
-      !((switches().tp_fold.load(std::memory_order_relaxed) >> mode) & 1)) {
-    const char *lo = reinterpret_cast<const char*>(t_wupd.grads), *o = reinterpret_cast<const char*>(out);
-    if (o >= lo && o + per * sizeof(float) <= lo + t_wupd.bytes) {
-      const size_t off = (size_t)(o - lo) / sizeof(float);
-      red_out = t_wupd.p_next + off; red_addend = t_wupd.p_cur + off; red_scale = -t_wupd.lr;
-      if (t_wupd.spans) t_wupd.spans->push_back(DybSpan{off, per});
-    }
+  // 1: the phase-separated loop (also what the phase probe and weight gradients over maps too small for the branch-free pixel walk use)
+  p.pipe = (tpk >= 2 && !g.probe && !(mode == MODE_WGRAD && TPK / g.Wo >= g.Ho)) ? (tpk >= 3 ? 2 : 1) : 0;
+  // in-kernel fold ("tp_fold", a bit per mode): the pipelined kernel, plain slabs (not the compact stride-2 form)
+  const bool fold = fold_in_kernel(c, p, !g.compact && p.pipe != 0 && ((dyb_switch(DYB_SW_tp_fold) >> mode) & 1));
+  p.exit = g.compact ? EXIT_SCATTER                   // (compact: always through the scatter fold)
+           : g.nsplit == 1 ? EXIT_DIRECT
+           : fold ? EXIT_KERNEL_FOLD                  // the result (and, forward, its statistics) leaves with the last workgroup of every tile
+           : c.nslabs ? EXIT_RAW_SLABS : EXIT_FOLD_LAUNCH;
+  route_result(c, p);
+  plan_weight_update(c, p);
+  if (stats_fusable && (p.exit == EXIT_DIRECT || p.exit == EXIT_KERNEL_FOLD)) {
+    g.gn_part = c.stats_part;
+    p.stats_nrec = stats_records;
   }
-  // (an UNSPLIT one: the epilogue writes the fast-weight step, or applies Adam - which only the pipelined loop forms carry: with pipe == 0
-  // an Adam scope is declined, the plain gradient goes to the gradient arena and the streaming Adam pass covers it, as no span is pushed)
-  if (mode == MODE_WGRAD && t_wupd.grads && !split && !g.compact && !addend && (!t_wupd.adam_m || pipe != 0)) {
-    const char *lo = reinterpret_cast<const char*>(t_wupd.grads), *o = reinterpret_cast<const char*>(out);
-    if (o >= lo && o + per * sizeof(float) <= lo + t_wupd.bytes) {
-      const size_t off = (size_t)(o - lo) / sizeof(float);
-      g.out = t_wupd.p_next + off;
-      g.addend = t_wupd.p_cur + off;
-      g.out_scale = -t_wupd.lr;
-      if (t_wupd.adam_m) {
-        g.adam_m = t_wupd.adam_m + off; g.adam_v = t_wupd.adam_v + off; g.adam_sc = t_wupd.adam_sc;
-        g.adam_b1 = t_wupd.b1; g.adam_b2 = t_wupd.b2; g.adam_eps = t_wupd.eps;
-        g.out_scale = 0.f;                  // (only marks the launch as a fused update for the byte accounting)
-      }
-      if (t_wupd.spans) t_wupd.spans->push_back(DybSpan{off, per});
-    }
-  }
-  // in-kernel fold ("tp_fold"): a counter region in scope, the pipelined kernel, plain slabs (not the compact stride-2 form)
-  const bool fold = split && !g.compact && pipe != 0 && t_conv_sync.ctr && (long)grid.x * grid.y * R.n <= (long)t_conv_sync.nwords &&
-                    !(raw_slabs_out && mode != MODE_FWD) && ((switches().tp_fold.load(std::memory_order_relaxed) >> mode) & 1);   // bit per mode
-  g.fold_out = nullptr; g.fold_addend = nullptr; g.fold_ctr = nullptr;
-  if (fold) {
-    g.fold_out = out; g.fold_addend = addend; g.fold_ctr = t_conv_sync.ctr;
-    switches().stat_folds.fetch_add(1, std::memory_order_relaxed);
-  }
-  g.gn_part = nullptr;
-  if (stats_nrec) *stats_nrec = 0;
-  if (stats_fusable && (!split || fold)) {
-    g.gn_part = stats_part;
-    *stats_nrec = stats_records;
-  }
-  const bool bf = dyb_bf16_current();
-  DYB_REQUIRE(!bf || pipe != 0, DYB_ERR_UNSUPPORTED);
-  DYB_REQUIRE(!g.adam_m || pipe != 0, DYB_ERR_UNSUPPORTED);        // (the Adam epilogue lives in the pipelined forms; a scope is declined above)
-  GnFwdFuse nf{};
-  if (nfuse) nf = *nfuse;
-  DYB_REQUIRE(!nfuse || d.N <= 64, DYB_ERR_UNSUPPORTED);
+  DYB_REQUIRE(!p.bf || p.pipe != 0, DYB_ERR_UNSUPPORTED);
+  DYB_REQUIRE(!g.adam_m || p.pipe != 0, DYB_ERR_UNSUPPORTED);        // (the Adam epilogue lives in the pipelined forms; a scope is declined above)
+  DYB_REQUIRE(p.family != FAM_STEM || (!c.nfuse && form == 2 && !p.bf), DYB_ERR_UNSUPPORTED);
   // "tp_occ" = k > 0: at most k workgroups of this launch per CU - unused dynamic LDS makes a (k+1)-th not fit (160 KiB per CU)
-  unsigned lds_pad = 0;
-  if (const int occ = switches().tp_occ.load(std::memory_order_relaxed); occ > 0) {
-    const unsigned lds_static = 2u * TPK * (unsigned)(TM + 4 + TN + 4) * 4u + (nfuse ? 64u * DYB_GN_GROUPS * 2u * 12u : 24u);
+  if (const int occ = dyb_switch(DYB_SW_tp_occ); occ > 0) {
+    const unsigned lds_static = 2u * TPK * (unsigned)(TM + 4 + TN + 4) * 4u + (c.nfuse ? 64u * DYB_GN_GROUPS * 2u * 12u : 24u);
     const unsigned want = 163840u / (unsigned)occ - 1024u;
-    if (want > lds_static) lds_pad = want - lds_static;
+    if (want > lds_static) p.lds = want - lds_static;
   }
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  timing_acquire(d, &ev0, &ev1, mode == MODE_FWD ? 't' : mode == MODE_DGRAD ? 'u' : 'v', g.nsplit, g.adam_m ? 2 : (g.out_scale != 1.f ? 1 : 0));
-#define DYB_TP_LAUNCH3(M_, FA_, WM_, WN_, P_)                                                                                      \
-  do {                                                                                                                             \
-    if (ev0) hipExtLaunchKernelGGL((igemm_tp_kernel<M_, FA_, WM_, WN_, P_>), grid, dim3(256), lds_pad, st, ev0, ev1, 0, g, nf, R); \
-    else hipLaunchKernelGGL((igemm_tp_kernel<M_, FA_, WM_, WN_, P_>), grid, dim3(256), lds_pad, st, g, nf, R);                     \
-  } while (0)
-#define DYB_TP_LAUNCH2(M_, FA_, WM_, WN_)                 \
-  do {                                                    \
-    if (bf) DYB_TP_LAUNCH_BF(M_, FA_, WM_, WN_);          \
-    else if (pipe == 2) DYB_TP_LAUNCH3(M_, FA_, WM_, WN_, 2);  \
-    else if (pipe) DYB_TP_LAUNCH3(M_, FA_, WM_, WN_, 1);  \
-    else DYB_TP_LAUNCH3(M_, FA_, WM_, WN_, 0);            \
-  } while (0)
-#define DYB_TP_LAUNCH_BF(M_, FA_, WM_, WN_)                                                                                          \
-  do {                                                                                                                             \
-    if (ev0) hipExtLaunchKernelGGL((igemm_tp_kernel<M_, FA_, WM_, WN_, 1, true>), grid, dim3(256), lds_pad, st, ev0, ev1, 0, g, nf, R); \
-    else hipLaunchKernelGGL((igemm_tp_kernel<M_, FA_, WM_, WN_, 1, true>), grid, dim3(256), lds_pad, st, g, nf, R);                     \
-  } while (0)
-#define DYB_TP_LAUNCH(M_, FA_)                        \
-  do {                                                \
-    if (form == 0) DYB_TP_LAUNCH2(M_, FA_, 2, 2);     \
-    else if (form == 1) DYB_TP_LAUNCH2(M_, FA_, 1, 4); \
-    else DYB_TP_LAUNCH2(M_, FA_, 4, 1);               \
-  } while (0)
-  if (mode == MODE_FWD && d.C == 4) {
-    DYB_REQUIRE(!nfuse && form == 2 && !bf, DYB_ERR_UNSUPPORTED);
-    if (ev0) hipExtLaunchKernelGGL((igemm_tp_kernel<MODE_FWD, false, 4, 1, 1, false, true>), grid, dim3(256), lds_pad, st, ev0, ev1, 0, g, nf, R);
-    else hipLaunchKernelGGL((igemm_tp_kernel<MODE_FWD, false, 4, 1, 1, false, true>), grid, dim3(256), lds_pad, st, g, nf, R);
-  } else if (mode == MODE_FWD) {
-    if (nfuse) DYB_TP_LAUNCH(MODE_FWD, true);
-    else DYB_TP_LAUNCH(MODE_FWD, false);
-  } else if (mode == MODE_DGRAD) {
-    DYB_REQUIRE(!nfuse, DYB_ERR_UNSUPPORTED);
-    DYB_TP_LAUNCH(MODE_DGRAD, false);
-  } else {
-    if (nfuse) DYB_TP_LAUNCH(MODE_WGRAD, true);
-    else DYB_TP_LAUNCH(MODE_WGRAD, false);
-  }
-#undef DYB_TP_LAUNCH
-#undef DYB_TP_LAUNCH2
-#undef DYB_TP_LAUNCH3
-#undef DYB_TP_LAUNCH_BF
-  DYB_CHECK_LAUNCH();
-  if (g.compact) {
-    const size_t tot4 = (size_t)g.M * g.Ncols / 4;
-    int blocks = (int)((tot4 + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(fold_scatter_s2_kernel, dim3(blocks, 1, R.n), dim3(256), 0, st, reinterpret_cast<const float4*>(ws), g.nsplit, per / 4,
-                       reinterpret_cast<const float4*>(addend), reinterpret_cast<float4*>(out), d.N, d.H, d.W, g.Ncols / 4, Hc, Wc, R);
-    DYB_CHECK_LAUNCH();
-    return DYB_OK;
-  }
-  if (fold) return DYB_OK;                       // the result (and, forward, its statistics) left with the last workgroup of every tile
-  if (split) {
-    if (raw_slabs_out) { *raw_slabs_out = g.nsplit; return DYB_OK; }
-    size_t n4 = per / 4;
-    int blocks = (int)((n4 + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks, 1, R.n), dim3(256), 0, st, reinterpret_cast<const float4*>(ws),
-                       reinterpret_cast<const float4*>(red_addend), reinterpret_cast<float4*>(red_out), g.nsplit, n4, R, red_scale);
-    DYB_CHECK_LAUNCH();
-  }
+  p.tag = "tuv"[mode];
+  p.timing_upd = g.adam_m ? 2 : (g.out_scale != 1.f ? 1 : 0);
   return DYB_OK;
 }
 
-// Runs one mode.  If `raw_slabs_out` is non-null and the policy picks nsplit>1 the slabs are left
-// in the workspace un-reduced and *raw_slabs_out = nsplit (caller folds them, e.g. inside the
-// GroupNorm statistics kernel); otherwise the result lands in `out`.
-static int run_igemm(int mode, const ConvDesc& d, const float* A, const float* B, float* out, const float* addend,
-                     void* ws, size_t ws_bytes, int* raw_slabs_out, hipStream_t st, const GnBwdFuse* fuse = nullptr,
-                     const GnFwdFuse* nfuse = nullptr, float* stats_part = nullptr, int* stats_nrec = nullptr, const float* A2 = nullptr,
-                     const float* B2 = nullptr) {
-  DYB_REQUIRE(A && B && out, DYB_ERR_ARG);
-  IgemmArgs g{};
-  int rc = fill_args(g, d, mode);
-  if (rc != DYB_OK) return rc;
-  g.A = A; g.B = B;
-  if (stats_nrec) *stats_nrec = 0;
-  if (A2 || B2) {            // operand pair: one K loop over both (latency form without fused loaders only - dyb_conv_pair_supported)
-    DYB_REQUIRE(A2 && B2 && !fuse && !nfuse && !tp_eligible(mode, d, nullptr) && !dyb_bf16_current(), DYB_ERR_UNSUPPORTED);
-    g.A2 = A2; g.B2 = B2;
-    g.ktiles = 2 * g.ktiles1;
-  } else if (tp_eligible(mode, d, fuse)) return run_igemm_tp(mode, d, g, out, addend, ws, ws_bytes, raw_slabs_out, st, nfuse, stats_part, stats_nrec);
-  g.nsplit = choose_split(g, ws ? ws_bytes / sizeof(float) : 0, mode, raw_slabs_out != nullptr && mode != MODE_FWD);
-  g.tiles_per_split = dyb_cdiv(g.ktiles, g.nsplit);
-  g.nsplit = dyb_cdiv(g.ktiles, g.tiles_per_split);       // drop empty tail splits
-  if (raw_slabs_out) *raw_slabs_out = 1;
-  const bool split = g.nsplit > 1;
-  g.out = split ? reinterpret_cast<float*>(ws) : out;
-  g.addend = split ? nullptr : addend;
-  const DybRep& R = dyb_rep_current();
-  dim3 grid(dyb_cdiv(g.M, BM), dyb_cdiv(g.Ncols, BN), g.nsplit * R.n);
-  // in-kernel split-K fold ("lat_fold": a counter region in scope; fp32 form - its epilogue goes through LDS) and, forward of one
-  // image, the output's GroupNorm statistics with the tiles (one record per workgroup tile; what a layer's partial slot holds)
+static int plan_latency(const ConvCall& c, ConvPlan& p) {
+  const int mode = c.mode;
+  IgemmArgs& g = p.g;
+  p.family = FAM_LATENCY;
   // the fp32 epilogue addresses a result matrix / slab through 32-bit byte offsets (TP_OOB = 2^31 marks "past the end"): larger is refused
-  // rather than silently dropped (ADVICE r5)
-  DYB_REQUIRE(dyb_bf16_current() || (size_t)g.M * g.Ncols * sizeof(float) < 0x7fffffffu, DYB_ERR_UNSUPPORTED);
-  const bool lat = !dyb_bf16_current() && switches().lat_fold.load(std::memory_order_relaxed);
-  // (not where the caller's next kernel folds the slabs while it reads them anyway: a gradient handed on as raw slabs)
-  const bool kfold = split && lat && t_conv_sync.ctr && (long)grid.x * grid.y * R.n <= (long)t_conv_sync.nwords &&
-                     !(raw_slabs_out && mode != MODE_FWD);
-  g.fold_out = nullptr; g.fold_addend = nullptr; g.fold_ctr = nullptr;
-  if (kfold) {
-    g.fold_out = out; g.fold_addend = addend; g.fold_ctr = t_conv_sync.ctr;
-    switches().stat_folds.fetch_add(1, std::memory_order_relaxed);
+  // rather than silently dropped
+  p.slab_floats = (size_t)g.M * g.Ncols;
+  DYB_REQUIRE(p.bf || p.slab_floats * sizeof(float) < 0x7fffffffu, DYB_ERR_UNSUPPORTED);
+  const size_t ws_floats = c.ws ? c.ws_bytes / sizeof(float) : 0;
+  finish_split(g, choose_split(g, ws_floats, mode, c.nslabs != nullptr && mode != MODE_FWD), p.slab_floats, ws_floats);
+  p.grid = dim3(dyb_cdiv(g.M, BM), dyb_cdiv(g.Ncols, BN), g.nsplit * dyb_rep_current().n);
+  // in-kernel split-K fold ("lat_fold": fp32 form - its epilogue goes through LDS) and, forward of one image, the output's GroupNorm
+  // statistics with the tiles (one record per workgroup tile)
+  const bool lat = !p.bf && dyb_switch(DYB_SW_lat_fold);
+  const bool kfold = fold_in_kernel(c, p, lat);
+  p.exit = g.nsplit == 1 ? EXIT_DIRECT : kfold ? EXIT_KERNEL_FOLD : c.nslabs ? EXIT_RAW_SLABS : EXIT_FOLD_LAUNCH;
+  route_result(c, p);
+  plan_weight_update(c, p);
+  const int records = (int)(p.grid.x * p.grid.y);
+  if (stats_fit(c, g, records) && lat && (p.exit == EXIT_DIRECT || kfold) && c.d.K % 64 == 0 && !c.A2) {
+    g.gn_part = c.stats_part;
+    p.stats_nrec = records;
   }
-  // "fuse_fast" in the latency form (one sequence): the finished weight-gradient tile - unsplit, or folded in-kernel by the last workgroup
-  // to arrive, or folded by the fold launch below - leaves p_next = p_cur - lr * g instead of g (see DybWgradUpdateScope)
-  const float* red_addend = addend;
-  float* red_out = out;
-  float red_scale = 1.f;
-  if (mode == MODE_WGRAD && t_wupd.grads && !t_wupd.adam_m && !dyb_bf16_current() && !A2 && !addend && !raw_slabs_out) {
-    const char *lo = reinterpret_cast<const char*>(t_wupd.grads), *o = reinterpret_cast<const char*>(out);
-    const size_t cnt = (size_t)g.M * g.Ncols;
-    if (o >= lo && o + cnt * sizeof(float) <= lo + t_wupd.bytes) {
-      const size_t off = (size_t)(o - lo) / sizeof(float);
-      if (!split) { g.out = t_wupd.p_next + off; g.addend = t_wupd.p_cur + off; g.out_scale = -t_wupd.lr; }
-      else if (kfold) { g.fold_out = t_wupd.p_next + off; g.fold_addend = t_wupd.p_cur + off; g.out_scale = -t_wupd.lr; }
-      else { red_out = t_wupd.p_next + off; red_addend = t_wupd.p_cur + off; red_scale = -t_wupd.lr; }
-      if (t_wupd.spans) t_wupd.spans->push_back(DybSpan{off, cnt});
-    }
-  }
-  g.gn_part = nullptr;
-  if (mode == MODE_FWD && stats_part && stats_nrec && lat && d.N == 1 && (!split || kfold) && d.K >= 64 && d.K % 64 == 0 && dyb_is_pow2(d.K) &&
-      !A2 && (int)(grid.x * grid.y) <= (g.Ho * g.Wo < 256 ? g.Ho * g.Wo : 256)) {
-    g.gn_part = stats_part;
-    *stats_nrec = (int)(grid.x * grid.y);
-  }
-  GnBwdFuse f{};
-  GnFwdFuse nf{};
-  if (fuse) f = *fuse;
-  if (nfuse) nf = *nfuse;
-  DYB_REQUIRE(!(fuse || nfuse) || d.N <= 64, DYB_ERR_UNSUPPORTED);
-  const dim3 blk(256);
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  timing_acquire(d, &ev0, &ev1, mode == MODE_FWD ? 'f' : mode == MODE_DGRAD ? 'd' : 'w', g.nsplit);
-  const bool bf = dyb_bf16_current();
-#define DYB_IGEMM_LAUNCH1(M_, GB_, FA_, BF_)                                                                           \
-  do {                                                                                                                 \
-    if (ev0) hipExtLaunchKernelGGL((igemm_mfma_kernel<M_, GB_, FA_, BF_>), grid, blk, 0, st, ev0, ev1, 0, g, f, nf, R); \
-    else hipLaunchKernelGGL((igemm_mfma_kernel<M_, GB_, FA_, BF_>), grid, blk, 0, st, g, f, nf, R);                    \
-  } while (0)
-#define DYB_IGEMM_LAUNCH(M_, GB_, FA_)              \
-  do {                                              \
-    if (bf) DYB_IGEMM_LAUNCH1(M_, GB_, FA_, true);  \
-    else DYB_IGEMM_LAUNCH1(M_, GB_, FA_, false);    \
-  } while (0)
-  if (mode == MODE_FWD) {
-    DYB_REQUIRE(!fuse, DYB_ERR_UNSUPPORTED);
-    if (nfuse) DYB_IGEMM_LAUNCH(MODE_FWD, false, true);
-    else DYB_IGEMM_LAUNCH(MODE_FWD, false, false);
-  } else if (mode == MODE_DGRAD) {
-    DYB_REQUIRE(!nfuse, DYB_ERR_UNSUPPORTED);
-    if (fuse) DYB_IGEMM_LAUNCH(MODE_DGRAD, true, false);
-    else DYB_IGEMM_LAUNCH(MODE_DGRAD, false, false);
-  } else {
-    if (fuse && nfuse) DYB_IGEMM_LAUNCH(MODE_WGRAD, true, true);
-    else if (fuse) DYB_IGEMM_LAUNCH(MODE_WGRAD, true, false);
-    else if (nfuse) DYB_IGEMM_LAUNCH(MODE_WGRAD, false, true);
-    else DYB_IGEMM_LAUNCH(MODE_WGRAD, false, false);
-  }
-#undef DYB_IGEMM_LAUNCH
-#undef DYB_IGEMM_LAUNCH1
-  DYB_CHECK_LAUNCH();
-  if (kfold) return DYB_OK;                      // folded by the last workgroup of every tile
-  if (split) {
-    if (raw_slabs_out) { *raw_slabs_out = g.nsplit; return DYB_OK; }
-    size_t n4 = (size_t)g.M * g.Ncols / 4;
-    int blocks = (int)((n4 + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks, 1, R.n), dim3(256), 0, st, reinterpret_cast<const float4*>(ws),
-                       reinterpret_cast<const float4*>(red_addend), reinterpret_cast<float4*>(red_out), g.nsplit, n4, R, red_scale);
-    DYB_CHECK_LAUNCH();
-  }
+  p.tag = "fdw"[mode];
   return DYB_OK;
+}
+
+static int plan_conv(const ConvCall& c, ConvPlan& p) {
+  DYB_REQUIRE(c.A && c.B && c.out, DYB_ERR_ARG);
+  p = ConvPlan{};
+  IgemmArgs& g = p.g;
+  int rc = fill_args(g, c.d, c.mode);
+  if (rc != DYB_OK) return rc;
+  g.A = c.A; g.B = c.B;
+  // fused loaders: at most 64 images; the GroupNorm backward belongs to a gradient's dy operand, the producer's GroupNorm to an activation operand
+  DYB_REQUIRE(!(c.fuse || c.nfuse) || c.d.N <= 64, DYB_ERR_UNSUPPORTED);
+  DYB_REQUIRE(!(c.fuse && c.mode == MODE_FWD) && !(c.nfuse && c.mode == MODE_DGRAD), DYB_ERR_UNSUPPORTED);
+  if (c.fuse) p.f = *c.fuse;
+  if (c.nfuse) p.nf = *c.nfuse;
+  p.bf = dyb_bf16_current();
+  const int tpk = dyb_switch(DYB_SW_tp_kernel);
+  const bool tp = tp_eligible(c.mode, c.d, g.Ho, g.Wo, tpk, p.bf, c.fuse != nullptr);
+  if (c.A2 || c.B2) {            // operand pair: one K loop over both
+    DYB_REQUIRE(c.A2 && c.B2 && !c.fuse && !c.nfuse && !tp && !p.bf, DYB_ERR_UNSUPPORTED);
+    g.A2 = c.A2; g.B2 = c.B2;
+    g.ktiles = 2 * g.ktiles1;
+  }
+  return tp ? plan_throughput(c, p, tpk) : plan_latency(c, p);
+}
+
+// ---- launches --------------------------------------------------------------------------------------------------------
+// Every kernel of this file starts here: with a (start, stop) event pair on its own dispatch where a timing scope handed one out
+// (or a caller's completion event as the stop event alone), plainly otherwise.
+template <class... KA>
+static void launch_kernel(void (*kernel)(KA...), dim3 grid, dim3 block, unsigned lds, hipStream_t st, hipEvent_t e0, hipEvent_t e1, KA... a) {
+  if (e0 || e1) hipExtLaunchKernelGGL(kernel, grid, block, lds, st, e0, e1, 0, a...);
+  else hipLaunchKernelGGL(kernel, grid, block, lds, st, a...);
+}
+static int fold_blocks(size_t n4) { return (int)std::min<size_t>((n4 + 255) / 256, 2048); }
+// out = addend + scale * sum_z slabs[z] (no addend: the plain sum) over n floats (n % 4 == 0)
+static int launch_fold(const void* slabs, int nslabs, size_t n, const float* addend, float* out, float scale, hipStream_t st) {
+  const DybRep& R = dyb_rep_current();
+  launch_kernel(splitk_reduce_kernel, dim3(fold_blocks(n / 4), 1, R.n), dim3(256), 0, st, nullptr, nullptr,
+                reinterpret_cast<const float4*>(slabs), reinterpret_cast<const float4*>(addend), reinterpret_cast<float4*>(out), nslabs, n / 4,
+                R, scale);
+  DYB_CHECK_LAUNCH();
+  return DYB_OK;
+}
+int dyb_splitk_fold(const float* slabs, int nslabs, size_t n, const float* addend, float* out, hipStream_t st) {
+  return launch_fold(slabs, nslabs, n, addend, out, 1.f, st);
+}
+
+// run time -> template arguments, one rung per choice
+template <int M, bool FA, int WM, int WN, int PIPE, bool BF = false, bool C4 = false>
+static void launch_tp(const ConvPlan& p, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  launch_kernel(igemm_tp_kernel<M, FA, WM, WN, PIPE, BF, C4>, p.grid, dim3(256), p.lds, st, e0, e1, p.g, p.nf, dyb_rep_current());
+}
+template <int M, bool FA, int WM, int WN>
+static void launch_tp_loop(const ConvPlan& p, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  if (p.bf) launch_tp<M, FA, WM, WN, 1, true>(p, st, e0, e1);
+  else if (p.pipe == 2) launch_tp<M, FA, WM, WN, 2>(p, st, e0, e1);
+  else if (p.pipe) launch_tp<M, FA, WM, WN, 1>(p, st, e0, e1);
+  else launch_tp<M, FA, WM, WN, 0>(p, st, e0, e1);
+}
+template <int M, bool FA>
+static void launch_tp_form(const ConvPlan& p, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  if (p.form == 0) launch_tp_loop<M, FA, 2, 2>(p, st, e0, e1);
+  else if (p.form == 1) launch_tp_loop<M, FA, 1, 4>(p, st, e0, e1);
+  else launch_tp_loop<M, FA, 4, 1>(p, st, e0, e1);
+}
+static void launch_throughput(int mode, bool fa, const ConvPlan& p, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  if (p.family == FAM_STEM) launch_tp<MODE_FWD, false, 4, 1, 1, false, true>(p, st, e0, e1);
+  else if (mode == MODE_FWD) fa ? launch_tp_form<MODE_FWD, true>(p, st, e0, e1) : launch_tp_form<MODE_FWD, false>(p, st, e0, e1);
+  else if (mode == MODE_DGRAD) launch_tp_form<MODE_DGRAD, false>(p, st, e0, e1);
+  else fa ? launch_tp_form<MODE_WGRAD, true>(p, st, e0, e1) : launch_tp_form<MODE_WGRAD, false>(p, st, e0, e1);
+}
+template <int M, bool GB, bool FA>
+static void launch_lat(const ConvPlan& p, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  const auto kernel = p.bf ? igemm_mfma_kernel<M, GB, FA, true> : igemm_mfma_kernel<M, GB, FA, false>;
+  launch_kernel(kernel, p.grid, dim3(256), 0, st, e0, e1, p.g, p.f, p.nf, dyb_rep_current());
+}
+static void launch_latency(int mode, bool gb, bool fa, const ConvPlan& p, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  if (mode == MODE_FWD) fa ? launch_lat<MODE_FWD, false, true>(p, st, e0, e1) : launch_lat<MODE_FWD, false, false>(p, st, e0, e1);
+  else if (mode == MODE_DGRAD) gb ? launch_lat<MODE_DGRAD, true, false>(p, st, e0, e1) : launch_lat<MODE_DGRAD, false, false>(p, st, e0, e1);
+  else if (gb) fa ? launch_lat<MODE_WGRAD, true, true>(p, st, e0, e1) : launch_lat<MODE_WGRAD, true, false>(p, st, e0, e1);
+  else fa ? launch_lat<MODE_WGRAD, false, true>(p, st, e0, e1) : launch_lat<MODE_WGRAD, false, false>(p, st, e0, e1);
+}
+
+// Carries a plan out.  No policy here; the only failure is a failed launch, and nothing is reported before the launches are issued.
+static int issue_conv(const ConvCall& c, const ConvPlan& p, hipStream_t st) {
+  const IgemmArgs& g = p.g;
+  const ConvDesc& d = c.d;
+  const DybRep& R = dyb_rep_current();
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  timing_acquire(d, &e0, &e1, p.tag, g.nsplit, p.timing_upd);
+  if (p.family == FAM_LATENCY) launch_latency(c.mode, c.fuse != nullptr, c.nfuse != nullptr, p, st, e0, e1);
+  else launch_throughput(c.mode, c.nfuse != nullptr, p, st, e0, e1);
+  DYB_CHECK_LAUNCH();
+  if (p.exit == EXIT_SCATTER) {
+    launch_kernel(fold_scatter_s2_kernel, dim3(fold_blocks((size_t)g.M * g.Ncols / 4), 1, R.n), dim3(256), 0, st, nullptr, nullptr,
+                  reinterpret_cast<const float4*>(c.ws), g.nsplit, p.slab_floats / 4, reinterpret_cast<const float4*>(c.addend),
+                  reinterpret_cast<float4*>(c.out), d.N, d.H, d.W, g.Ncols / 4, (d.H + 1) >> 1, (d.W + 1) >> 1, R);
+    DYB_CHECK_LAUNCH();
+  } else if (p.exit == EXIT_FOLD_LAUNCH) {
+    int rc = launch_fold(c.ws, g.nsplit, p.slab_floats, p.fold_addend, p.fold_out, p.fold_scale, st);
+    if (rc != DYB_OK) return rc;
+  }
+  // the span goes to the caller's list so that its streaming pass leaves the range out
+  if (p.upd != UPD_NONE && t_wupd.spans) t_wupd.spans->push_back(DybSpan{p.upd_off, p.upd_n});
+  if (p.exit == EXIT_KERNEL_FOLD) switches().v[DYB_SW_stat_folds].fetch_add(1, std::memory_order_relaxed);
+  if (c.nslabs) *c.nslabs = p.exit == EXIT_RAW_SLABS ? g.nsplit : 1;
+  if (c.stats_nrec) *c.stats_nrec = p.stats_nrec;
+  return DYB_OK;
+}
+static int run_conv(const ConvCall& c, hipStream_t st) {
+  ConvPlan p;
+  int rc = plan_conv(c, p);
+  return rc != DYB_OK ? rc : issue_conv(c, p, st);
 }
 
 // Operand pairs (internal: the tangent passes of hvp_engine.inc).  mode 0 / 1 / 2 = forward / data gradient / weight gradient:
@@ -1950,13 +1924,16 @@ static int run_igemm(int mode, const ConvDesc& d, const float* A, const float* B
 //   weight gradient  out = wgrad(a1, b1) + wgrad(a2, b2)               a = activations, b = output gradients
 // as one launch with a K loop over both pairs (and one split-K fold instead of two folds and an add).
 bool dyb_conv_pair_supported(int mode, const ConvDesc& d) {
-  return switches().pair.load(std::memory_order_relaxed) && !tp_eligible(mode, d, nullptr) && !dyb_bf16_current();
+  return dyb_switch(DYB_SW_pair) && !dyb_bf16_current() &&
+         !tp_eligible(mode, d, conv_out_dim(d.H, d.R, d.stride, d.pad), conv_out_dim(d.W, d.S, d.stride, d.pad), dyb_switch(DYB_SW_tp_kernel), false, false);
 }
 int dyb_conv_pair(int mode, const ConvDesc& d, const float* a1, const float* b1, const float* a2, const float* b2, float* out,
                   const float* addend, void* ws, size_t ws_bytes, hipStream_t st) {
   DYB_REQUIRE(mode >= 0 && mode <= 2 && a2 && b2, DYB_ERR_ARG);
   DYB_REQUIRE(mode == MODE_DGRAD || !addend, DYB_ERR_UNSUPPORTED);
-  return run_igemm(mode, d, a1, b1, out, addend, ws, ws_bytes, nullptr, st, nullptr, nullptr, nullptr, nullptr, a2, b2);
+  ConvCall c = conv_call(mode, d, a1, b1, out, ws, ws_bytes);
+  c.A2 = a2; c.B2 = b2; c.addend = addend;
+  return run_conv(c, st);
 }
 
 extern "C" int dyb_debug_conv_pair(int mode, const float* a1, const float* b1, const float* a2, const float* b2, float* out,
@@ -1970,25 +1947,29 @@ extern "C" int dyb_debug_conv_pair(int mode, const float* a1, const float* b1, c
 
 int dyb_conv_fwd_raw(const ConvDesc& d, const float* x, const float* w, float* y, void* ws, size_t ws_bytes,
                      int* nslabs, hipStream_t st) {
-  return run_igemm(MODE_FWD, d, x, w, y, nullptr, ws, ws_bytes, nslabs, st);
+  ConvCall c = conv_call(MODE_FWD, d, x, w, y, ws, ws_bytes);
+  c.nslabs = nslabs;
+  return run_conv(c, st);
 }
 
 extern "C" int dyb_conv2d_nhwc_fwd(const float* x, const float* w, float* y, int N, int H, int W, int C, int K, int R,
                                    int S, int stride, int pad, void* ws, size_t ws_bytes, hipStream_t st) {
   ConvDesc d{N, H, W, C, K, R, S, stride, pad};
-  return run_igemm(MODE_FWD, d, x, w, y, nullptr, ws, ws_bytes, nullptr, st);
+  return run_conv(conv_call(MODE_FWD, d, x, w, y, ws, ws_bytes), st);
 }
 // dx = conv_transpose(dy, w) (+ addend, e.g. the gradient arriving over the residual edge)
 extern "C" int dyb_conv2d_nhwc_dgrad(const float* dy, const float* w, float* dx, const float* addend, int N, int H,
                                      int W, int C, int K, int R, int S, int stride, int pad, void* ws,
                                      size_t ws_bytes, hipStream_t st) {
   ConvDesc d{N, H, W, C, K, R, S, stride, pad};
-  return run_igemm(MODE_DGRAD, d, dy, w, dx, addend, ws, ws_bytes, nullptr, st);
+  ConvCall c = conv_call(MODE_DGRAD, d, dy, w, dx, ws, ws_bytes);
+  c.addend = addend;
+  return run_conv(c, st);
 }
 extern "C" int dyb_conv2d_nhwc_wgrad(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K,
                                      int R, int S, int stride, int pad, void* ws, size_t ws_bytes, hipStream_t st) {
   ConvDesc d{N, H, W, C, K, R, S, stride, pad};
-  return run_igemm(MODE_WGRAD, d, x, dy, dw, nullptr, ws, ws_bytes, nullptr, st);
+  return run_conv(conv_call(MODE_WGRAD, d, x, dy, dw, ws, ws_bytes), st);
 }
 
 // Diagnostic (tools/tp_lab.py): one convolution mode for `nrep` sequence replicas in ONE launch, the way the native stepper issues
@@ -2012,9 +1993,7 @@ extern "C" int dyb_debug_conv_replicas(int mode, const float* x, const float* w,
   const size_t wsl = (ws_bytes / (size_t)nrep) & ~(size_t)255;
   arena(ws, wsl);
   DybRepScope scope(Rp);
-  if (mode == 0) return run_igemm(MODE_FWD, d, x, w, out, nullptr, ws, wsl, nullptr, st);
-  if (mode == 1) return run_igemm(MODE_DGRAD, d, dy, w, out, nullptr, ws, wsl, nullptr, st);
-  return run_igemm(MODE_WGRAD, d, x, dy, out, nullptr, ws, wsl, nullptr, st);
+  return run_conv(conv_call(mode, d, mode == MODE_DGRAD ? dy : x, mode == MODE_WGRAD ? dy : w, out, ws, wsl), st);
 }
 
 // ---- data / weight gradient with the GroupNorm backward of the conv's output formed in the loader ----
@@ -2041,10 +2020,8 @@ extern "C" int dyb_conv2d_nhwc_dgrad_gn(const float* dm, const float* y_gn, cons
                                         int W, int C, int K, int R, int S, int stride, int pad, void* ws, size_t ws_bytes,
                                         hipStream_t st) {
   ConvDesc d{N, H, W, C, K, R, S, stride, pad};
-  GnBwdFuse f{};
-  int rc = make_fuse(f, d, y_gn, stats, part, gamma, nullptr, nullptr);
-  if (rc != DYB_OK) return rc;
-  return run_igemm(MODE_DGRAD, d, dm, w, dx, addend, ws, ws_bytes, nullptr, st, &f);
+  GnBwdSrc src{dm, y_gn, stats, part, gamma, 0, 0};
+  return dyb_conv_dgrad_gn_raw(d, src, w, dx, addend, ws, ws_bytes, nullptr, st);
 }
 extern "C" int dyb_conv2d_nhwc_wgrad_gn(const float* x, const float* dm, const float* y_gn, const float* stats,
                                         const float* part, const float* gamma, float* dw, float* dgamma, float* dbeta,
@@ -2055,12 +2032,13 @@ extern "C" int dyb_conv2d_nhwc_wgrad_gn(const float* x, const float* dm, const f
   GnBwdFuse f{};
   int rc = make_fuse(f, d, y_gn, stats, part, gamma, dgamma, dbeta);
   if (rc != DYB_OK) return rc;
-  return run_igemm(MODE_WGRAD, d, x, dm, dw, nullptr, ws, ws_bytes, nullptr, st, &f);
+  ConvCall c = conv_call(MODE_WGRAD, d, x, dm, dw, ws, ws_bytes);
+  c.fuse = &f;
+  return run_conv(c, st);
 }
 bool dyb_conv_dgrad_k4_ok(const ConvDesc& d) {
-  const DybSwitches& sw = switches();                   // k4_bwd on: 1.40 -> 1.31 ms per backward
-  const int enabled = sw.k4_bwd.load(std::memory_order_relaxed), max_k = sw.k4_maxc.load(std::memory_order_relaxed);
-  const bool batch_ok = d.N == 1 || (sw.k4_batch.load(std::memory_order_relaxed) && d.N <= 64);
+  const int enabled = dyb_switch(DYB_SW_k4_bwd), max_k = dyb_switch(DYB_SW_k4_maxc);
+  const bool batch_ok = d.N == 1 || (dyb_switch(DYB_SW_k4_batch) && d.N <= 64);
   return enabled && !dyb_bf16_current() && !dyb_throughput_mode(d.N) && batch_ok && d.R == 1 && d.S == 1 && d.pad == 0 && d.stride == 1 && dyb_is_pow2(d.K) && d.K >= 128 &&
          d.K <= max_k && d.C % 128 == 0 && d.H * d.W <= 784;
 }
@@ -2081,18 +2059,13 @@ int dyb_conv_dgrad_k4(const ConvDesc& d, const GnBwdSrc& src, const float* w, co
                 d.N, tpi};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   timing_acquire(d, &ev0, &ev1, 'D');                 // bench.py's conv timing scope
-#define DYB_K4D_LAUNCH(MU_)                                                                                          \
-  do {                                                                                                               \
-    if (ev0) hipExtLaunchKernelGGL((igemm_k4_dgrad_kernel<MU_>), grid, dim3(256), 0, st, ev0, ev1, 0, g, f, R);      \
-    else if (done) hipExtLaunchKernelGGL((igemm_k4_dgrad_kernel<MU_>), grid, dim3(256), 0, st, nullptr, done, 0, g, f, R); \
-    else hipLaunchKernelGGL((igemm_k4_dgrad_kernel<MU_>), grid, dim3(256), 0, st, g, f, R);                          \
-  } while (0)
-  if (d.N == 1) DYB_K4D_LAUNCH(false);
-  else DYB_K4D_LAUNCH(true);
-#undef DYB_K4D_LAUNCH
+  // inside a timing scope the launch carries the timing pair, so the caller's completion event is a record of its own; outside one
+  // the launch carries that event itself
+  const bool timed = ev0 != nullptr;
+  if (!timed) ev1 = done;
+  launch_kernel(d.N == 1 ? igemm_k4_dgrad_kernel<false> : igemm_k4_dgrad_kernel<true>, grid, dim3(256), 0, st, ev0, ev1, g, f, R);
   DYB_CHECK_LAUNCH();
-  // inside a timing scope the launch carries the timing pair, so the caller's completion event is a record of its own
-  if (ev0 && done && hipEventRecord(done, st) != hipSuccess) return DYB_ERR_LAUNCH;
+  if (timed && done && hipEventRecord(done, st) != hipSuccess) return DYB_ERR_LAUNCH;
   *nch = tpi;                                  // row chunks per image
   *ncolb = (int)grid.y;
   return DYB_OK;
@@ -2102,10 +2075,10 @@ int dyb_conv_dgrad_gn_raw(const ConvDesc& d, const GnBwdSrc& src, const float* w
   GnBwdFuse f{};
   int rc = make_fuse(f, d, src.y, src.stats, src.part, src.gamma, nullptr, nullptr, src.nch, src.ncolb);
   if (rc != DYB_OK) return rc;
-  return run_igemm(MODE_DGRAD, d, src.dm, w, dx, addend, ws, ws_bytes, nslabs, st, &f);
+  ConvCall c = conv_call(MODE_DGRAD, d, src.dm, w, dx, ws, ws_bytes);
+  c.addend = addend; c.nslabs = nslabs; c.fuse = &f;
+  return run_conv(c, st);
 }
-static void make_nfuse(GnFwdFuse& nf, const ConvDesc& d, const float* partials, const float* stats_in, const float* gamma,
-                       const float* beta, float* stats_out, int relu);
 // ---- throughput schedule: plain gradient convolutions over a materialised dy (dyb_common.h) -----------------------------
 // workgroups per image the GroupNorm kernels' chunking may use when a launch covers several sequence replicas under the
 // throughput policy (0: the single-sequence sizing applies): "tp_gn_wgs" (1024) over all replicas of the launch
@@ -2113,57 +2086,47 @@ int dyb_gn_replica_share(int N) {
   if (!dyb_throughput_mode()) return 0;
   const int reps = dyb_rep_current().n;
   if (reps <= 1) return 0;
-  int w = switches().tp_gn_wgs.load(std::memory_order_relaxed) / (reps * (N > 0 ? N : 1));
+  int w = dyb_switch(DYB_SW_tp_gn_wgs) / (reps * (N > 0 ? N : 1));
   return w < 1 ? 1 : w;
 }
-// throughput schedule, GroupNorm backward: "tp_gn_onepass" 2 (default) = the one-pass kernel for every layer that qualifies (slabs
-// of several row chunks meet on a counter), 1 = only layers whose (image, group) slab is one workgroup, 0 = the two-launch
-// reduce + apply; "tp_gn_cap" = float4 per workgroup (0: 8 x "tp_gn_threads", the workgroup size 256 / 512 / 1024; tests force
-// several chunks on small shapes)
-int dyb_tp_gn_onepass() { return switches().tp_gn_onepass.load(std::memory_order_relaxed); }
-int dyb_tp_gn_cap() { return switches().tp_gn_cap.load(std::memory_order_relaxed); }
-int dyb_tp_gn_threads() { return switches().tp_gn_threads.load(std::memory_order_relaxed); }
-int dyb_tp_gn_poll() { return switches().tp_gn_poll.load(std::memory_order_relaxed); }
-int dyb_tp_gn_wt() { return switches().tp_gn_wt.load(std::memory_order_relaxed); }
 bool dyb_throughput_mode(int batch) {
-  const DybSwitches& sw = switches();
-  if (sw.rep_split.load(std::memory_order_relaxed) != 0 && dyb_rep_current().n >= sw.tp_min.load(std::memory_order_relaxed)) return true;
-  const int bmin = sw.tp_batch_min.load(std::memory_order_relaxed);
+  if (dyb_switch(DYB_SW_rep_split) != 0 && dyb_rep_current().n >= dyb_switch(DYB_SW_tp_min)) return true;
+  const int bmin = dyb_switch(DYB_SW_tp_batch_min);
   return bmin > 0 && batch >= bmin;
+}
+// ---- producer GroupNorm(+ReLU) applied in the loader (GnFwdFuse) ---------------------------------
+static void make_nfuse(GnFwdFuse& nf, const ConvDesc& d, const float* partials, const float* stats_in, const float* gamma,
+                       const float* beta, float* stats_out, int relu) {
+  nf.partials = partials; nf.stats_in = stats_in; nf.gamma = gamma; nf.beta = beta; nf.stats_out = stats_out;
+  nf.HW = d.H * d.W;
+  nf.nchunks = dyb_gn_fwd_chunks(d.N, nf.HW);
+  nf.eps = DYB_GN_EPS;
+  nf.relu = relu;
 }
 int dyb_conv_dgrad_plain_raw(const ConvDesc& d, const float* dy, const float* w, float* dx, const float* addend, void* ws,
                              size_t ws_bytes, int* nslabs, hipStream_t st) {
-  return run_igemm(MODE_DGRAD, d, dy, w, dx, addend, ws, ws_bytes, nslabs, st);
+  ConvCall c = conv_call(MODE_DGRAD, d, dy, w, dx, ws, ws_bytes);
+  c.addend = addend; c.nslabs = nslabs;
+  return run_conv(c, st);
 }
 int dyb_conv_wgrad_plain(const ConvDesc& d, const float* x, const float* y_prev, const float* stats_prev, const float* gamma_prev,
                          const float* beta_prev, const float* dy, float* dw, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (x) return run_igemm(MODE_WGRAD, d, x, dy, dw, nullptr, ws, ws_bytes, nullptr, st);
+  if (x) return run_conv(conv_call(MODE_WGRAD, d, x, dy, dw, ws, ws_bytes), st);
   DYB_REQUIRE(y_prev && stats_prev && gamma_prev && beta_prev && d.C % 16 == 0, DYB_ERR_ARG);
   GnFwdFuse nf{};
   make_nfuse(nf, d, nullptr, stats_prev, gamma_prev, beta_prev, nullptr, 1);
-  return run_igemm(MODE_WGRAD, d, y_prev, dy, dw, nullptr, ws, ws_bytes, nullptr, st, nullptr, &nf);
+  ConvCall c = conv_call(MODE_WGRAD, d, y_prev, dy, dw, ws, ws_bytes);
+  c.nfuse = &nf;
+  return run_conv(c, st);
 }
-// out = sum_z slabs[z] (+ addend) over n floats (n % 4 == 0)
-int dyb_splitk_fold(const float* slabs, int nslabs, size_t n, const float* addend, float* out, hipStream_t st) {
-  size_t n4 = n / 4;
-  int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  const DybRep& R = dyb_rep_current();
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks, 1, R.n), dim3(256), 0, st, reinterpret_cast<const float4*>(slabs),
-                     reinterpret_cast<const float4*>(addend), reinterpret_cast<float4*>(out), nslabs, n4, R, 1.f);
-  DYB_CHECK_LAUNCH();
-  return DYB_OK;
-}
-
 
 // ---- K4 host side ------------------------------------------------------------------------------------
 bool dyb_conv_k4_ok(const ConvDesc& d) {
   const int Ho = conv_out_dim(d.H, d.R, d.stride, d.pad), Wo = conv_out_dim(d.W, d.S, d.stride, d.pad);
-  const DybSwitches& sw = switches();
-  const int enabled = sw.k4.load(std::memory_order_relaxed), max_c = sw.k4_maxc.load(std::memory_order_relaxed);
+  const int enabled = dyb_switch(DYB_SW_k4), max_c = dyb_switch(DYB_SW_k4_maxc);
   // Cin <= 512: a K-step of this kernel costs ~1.9 us (measured: 8.6 / 11.8 / 20 us at 2 / 4 / 8 steps - every step is a
   // cold-L2 round trip), so beyond 4 steps the tiled kernel's split-K over more workgroups + the statistics launch is faster
-  const bool batch_ok = d.N == 1 || (sw.k4_batch.load(std::memory_order_relaxed) && d.N <= 64);
+  const bool batch_ok = d.N == 1 || (dyb_switch(DYB_SW_k4_batch) && d.N <= 64);
   return enabled && !dyb_bf16_current() && !dyb_throughput_mode(d.N) && batch_ok && d.R == 1 && d.S == 1 && d.pad == 0 && dyb_is_pow2(d.C) && d.C >= 128 && d.C <= max_c &&
          d.K % 128 == 0 && Ho * Wo <= 784;
 }
@@ -2181,33 +2144,14 @@ int dyb_conv_fwd_k4(const ConvDesc& d, const float* x, const float* w, float* y,
   if (nf) f = *nf;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   timing_acquire(d, &ev0, &ev1, 'F');
-#define DYB_K4_LAUNCH(FA_, MU_)                                                                                       \
-  do {                                                                                                                \
-    if (ev0) hipExtLaunchKernelGGL((igemm_k4_fwd_kernel<FA_, MU_>), grid, dim3(256), 0, st, ev0, ev1, 0, g, f, R);    \
-    else hipLaunchKernelGGL((igemm_k4_fwd_kernel<FA_, MU_>), grid, dim3(256), 0, st, g, f, R);                        \
-  } while (0)
-  if (d.N == 1) {
-    if (nf) DYB_K4_LAUNCH(true, false);
-    else DYB_K4_LAUNCH(false, false);
-  } else {
-    if (nf) DYB_K4_LAUNCH(true, true);
-    else DYB_K4_LAUNCH(false, true);
-  }
-#undef DYB_K4_LAUNCH
+  auto launch = [&](void (*kernel)(K4Args, GnFwdFuse, DybRep)) { launch_kernel(kernel, grid, dim3(256), 0, st, ev0, ev1, g, f, R); };
+  if (d.N == 1) launch(nf ? igemm_k4_fwd_kernel<true, false> : igemm_k4_fwd_kernel<false, false>);
+  else launch(nf ? igemm_k4_fwd_kernel<true, true> : igemm_k4_fwd_kernel<false, true>);
   DYB_CHECK_LAUNCH();
   *nchunks = (int)(g.tpi * grid.y);             // partial records per image
   return DYB_OK;
 }
 
-// ---- producer GroupNorm(+ReLU) applied in the loader (GnFwdFuse) ---------------------------------
-static void make_nfuse(GnFwdFuse& nf, const ConvDesc& d, const float* partials, const float* stats_in, const float* gamma,
-                       const float* beta, float* stats_out, int relu) {
-  nf.partials = partials; nf.stats_in = stats_in; nf.gamma = gamma; nf.beta = beta; nf.stats_out = stats_out;
-  nf.HW = d.H * d.W;
-  nf.nchunks = dyb_gn_fwd_chunks(d.N, nf.HW);
-  nf.eps = DYB_GN_EPS;
-  nf.relu = relu;
-}
 int dyb_conv_fwd_gnin_raw(const ConvDesc& d, const float* y_prev, const float* part_prev, int nch_prev,
                           const float* gamma_prev, const float* beta_prev, int relu_prev, float* stats_prev_out, const float* w,
                           float* y, void* ws, size_t ws_bytes, int* nslabs, hipStream_t st) {
@@ -2215,13 +2159,14 @@ int dyb_conv_fwd_gnin_raw(const ConvDesc& d, const float* y_prev, const float* p
   GnFwdFuse nf{};
   make_nfuse(nf, d, part_prev, nullptr, gamma_prev, beta_prev, stats_prev_out, relu_prev);
   if (nch_prev > 0) nf.nchunks = nch_prev;
-  return run_igemm(MODE_FWD, d, y_prev, w, y, nullptr, ws, ws_bytes, nslabs, st, nullptr, &nf);
+  ConvCall c = conv_call(MODE_FWD, d, y_prev, w, y, ws, ws_bytes);
+  c.nslabs = nslabs; c.nfuse = &nf;
+  return run_conv(c, st);
 }
 // Forward conv of one layer INCLUDING the GroupNorm statistics of its output: y and per-chunk (sum, sum of squares)
 // partials (*nchunks records of [G][2]).  x is a plain activation, or - part_prev != NULL - the producer's raw conv
 // output whose GroupNorm(+ReLU) is applied in the loader from its nch_prev partials.  Small 1x1 layers at batch 1 take
 // the single-launch K4 kernel; everything else is the tiled conv + dyb_groupnorm_stats (which folds the split-K slabs).
-extern "C" int dyb_groupnorm_stats(const float*, int, float*, float*, int, int, int, hipStream_t);
 extern "C" int dyb_conv2d_nhwc_fwd_gnstats(const float* x, const float* part_prev, int nch_prev, const float* gamma_prev,
                                            const float* beta_prev, int relu_prev, float* stats_prev_out, const float* w,
                                            float* y, float* partials, int* nchunks, int N, int H, int W, int C, int K, int R,
@@ -2237,7 +2182,9 @@ extern "C" int dyb_conv2d_nhwc_fwd_gnstats(const float* x, const float* part_pre
   }
   if (dyb_conv_k4_ok(d)) return dyb_conv_fwd_k4(d, x, w, y, partials, part_prev ? &nf : nullptr, nchunks, st);
   int nslabs = 1, nrec = 0;
-  int rc = run_igemm(MODE_FWD, d, x, w, y, nullptr, ws, ws_bytes, &nslabs, st, nullptr, part_prev ? &nf : nullptr, partials, &nrec);
+  ConvCall c = conv_call(MODE_FWD, d, x, w, y, ws, ws_bytes);
+  c.nslabs = &nslabs; c.nfuse = part_prev ? &nf : nullptr; c.stats_part = partials; c.stats_nrec = &nrec;
+  int rc = run_conv(c, st);
   if (rc != DYB_OK) return rc;
   if (nrec > 0) {                        // throughput kernel, no split: the statistics left with the tiles (igemm_tp.inc epilogue)
     *nchunks = nrec;
@@ -2270,7 +2217,9 @@ extern "C" int dyb_conv2d_nhwc_wgrad_gn_gnin(const float* y_prev, const float* s
   if (rc != DYB_OK) return rc;
   GnFwdFuse nf{};
   make_nfuse(nf, d, nullptr, stats_prev, gamma_prev, beta_prev, nullptr, relu_prev);
-  return run_igemm(MODE_WGRAD, d, y_prev, dm, dw, nullptr, ws, ws_bytes, nullptr, st, &f, &nf);
+  ConvCall c = conv_call(MODE_WGRAD, d, y_prev, dm, dw, ws, ws_bytes);
+  c.fuse = &f; c.nfuse = &nf;
+  return run_conv(c, st);
 }
 
 // Data gradient of conv (N,H,W,C,K,...) fused with the GroupNorm-backward reduce of the PRODUCER of its input (the
@@ -2278,8 +2227,6 @@ extern "C" int dyb_conv2d_nhwc_wgrad_gn_gnin(const float* y_prev, const float* s
 // is scratch.  Small 1x1 layers at batch 1 with DYB_K4_BWD=1 run as one launch (K4 dgrad); otherwise this is
 // dyb_conv2d_nhwc_dgrad_gn into dx_scratch followed by dyb_groupnorm_bwd_reduce.  *nch_p / *ncolb_p: layout of part_p
 // for the producer's own fused gradients (pass them on as nch / ncolb there).
-extern "C" int dyb_groupnorm_bwd_reduce(const float*, const float*, const float*, const float*, const float*, const float*, float*,
-                                        float*, int, int, int, int, hipStream_t);
 extern "C" int dyb_conv2d_nhwc_dgrad_gn_reduce(const float* dm, const float* y_gn, const float* stats, const float* part, int nch,
                                                int ncolb, const float* gamma, const float* w, const float* addend,
                                                const float* y_p, const float* out_p, const float* stats_p,
@@ -2316,8 +2263,12 @@ extern "C" int dyb_conv2d_nhwc_wgrad_gn_n(const float* x, const float* y_prev, c
   GnBwdFuse f{};
   int rc = make_fuse(f, d, y_gn, stats, part, gamma, dgamma, dbeta, nch, ncolb);
   if (rc != DYB_OK) return rc;
-  if (!y_prev) return run_igemm(MODE_WGRAD, d, x, dm, dw, nullptr, ws, ws_bytes, nullptr, st, &f);
+  ConvCall c = conv_call(MODE_WGRAD, d, y_prev ? y_prev : x, dm, dw, ws, ws_bytes);
+  c.fuse = &f;
   GnFwdFuse nf{};
-  make_nfuse(nf, d, nullptr, stats_prev, gamma_prev, beta_prev, nullptr, 1);
-  return run_igemm(MODE_WGRAD, d, y_prev, dm, dw, nullptr, ws, ws_bytes, nullptr, st, &f, &nf);
+  if (y_prev) {
+    make_nfuse(nf, d, nullptr, stats_prev, gamma_prev, beta_prev, nullptr, 1);
+    c.nfuse = &nf;
+  }
+  return run_conv(c, st);
 }

@@ -312,19 +312,16 @@ extern "C" int dyb_linear_bwd_dw(const float* const* dys, const int* lddys, cons
   // is one contiguous tensor of the arena (I == ldw for fc1 / fc2 / the decoder) - updated here, its span reported like a convolution's
   OuterUpd u{};
   const DybWgradUpdate& W = dyb_wgrad_update_current();
-  if (W.grads && I == ldw && switches_linear_fuse()) {
-    const char *lo = reinterpret_cast<const char*>(W.grads), *o = reinterpret_cast<const char*>(dw);
-    const size_t cnt = (size_t)O * ldw;
-    if (o >= lo && o + cnt * sizeof(float) <= lo + W.bytes) {
-      const size_t off = (size_t)(o - lo) / sizeof(float);
-      u.kind = W.adam_m ? 2 : 1;
-      u.p_cur = W.p_cur + off; u.p_next = W.p_next + off; u.lr = W.lr;
-      if (W.adam_m) { u.m = W.adam_m + off; u.v = W.adam_v + off; u.sc = W.adam_sc; u.b1 = W.b1; u.b2 = W.b2; u.eps = W.eps; }
-      if (W.spans) W.spans->push_back(DybSpan{off, cnt});
-    }
+  const size_t cnt = (size_t)O * ldw;
+  size_t off = 0;
+  if (I == ldw && switches_linear_fuse() && W.claims(dw, cnt, &off)) {
+    u.kind = W.adam_m ? 2 : 1;
+    u.p_cur = W.p_cur + off; u.p_next = W.p_next + off; u.lr = W.lr;
+    if (W.adam_m) { u.m = W.adam_m + off; u.v = W.adam_v + off; u.sc = W.adam_sc; u.b1 = W.b1; u.b2 = W.b2; u.eps = W.eps; }
   }
   hipLaunchKernelGGL(linear_outer_kernel, dim3(dyb_cdiv(I / 4, 64), dyb_cdiv(O, 4 * OUTER_ROWS), R.n), dim3(256), 0, st, a, T, B, I, O, dw,
                      ldw, db, u, R);
   DYB_CHECK_LAUNCH();
+  if (u.kind && W.spans) W.spans->push_back(DybSpan{off, cnt});      // reported once the launch that covers it is issued
   return DYB_OK;
 }

@@ -876,7 +876,7 @@ int dyb_zero_words(unsigned* p, int n, hipStream_t st) {
 // small caps
 static int onepass_threads(int cap) {
   if (cap <= 0) {
-    const int t = dyb_tp_gn_threads();
+    const int t = dyb_switch(DYB_SW_tp_gn_threads);
     return t >= 1024 ? 1024 : t >= 512 ? 512 : 256;
   }
   return cap > 512 * OP_IT ? 1024 : cap > 256 * OP_IT ? 512 : 256;
@@ -902,7 +902,7 @@ int dyb_gn_bwd_onepass(const float* din, int nslabs, size_t slab_stride, const f
   const int rows = dyb_cdiv(HW, k);
   DYB_REQUIRE(dyb_is_pow2(C) && C >= 64 && C <= 2048 && rows * (C / 16) <= 1024 * OP_IT && dyb_cdiv(HW, rows) == k, DYB_ERR_UNSUPPORTED);
   GnOnepass a{din, addend, out, y, stats, gamma, beta, dm == din ? nullptr : dm, dy, dgamma, dbeta, part, ctr, slab_stride, nslabs, HW, C,
-              rows, relu, dyb_tp_gn_poll() > 0 ? dyb_tp_gn_poll() : 1, dyb_tp_gn_wt()};
+              rows, relu, dyb_switch(DYB_SW_tp_gn_poll) > 0 ? dyb_switch(DYB_SW_tp_gn_poll) : 1, dyb_switch(DYB_SW_tp_gn_wt)};
   const DybRep& R = dyb_rep_current();
   const int items = rows * (C / 16);
   if (items <= 256 * OP_IT) hipLaunchKernelGGL(gn_bwd_onepass_kernel<256>, dim3(k, G, R.n), dim3(256), 0, st, a, R);

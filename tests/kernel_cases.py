@@ -375,6 +375,42 @@ def case_conv_inkernel_fold(be, N, H, W, C, K, R, stride, pad, seed=0):
     return after.value - before.value
 
 
+def case_conv_refusal_reports_nothing(be, seed=0):
+    """A refused launch reports nothing: with a fast-weight scope open over an arena that holds the layer's dw, the GroupNorm-fused
+    weight gradient at N = 65 (its loader form stops at 64 images) returns DYB_ERR_UNSUPPORTED - and no span was reported (the
+    stepper's streaming pass would leave that range out and the tensor's weights would silently not be updated), the in-kernel-fold
+    counter did not move, and neither the gradient arena nor p_next was written: nothing was launched."""
+    N, H, W, C, Kc = 65, 4, 4, 16, 16
+    rng = _rng(seed)
+    n = C * Kc
+    f32 = lambda *shape: be.dev(rng.standard_normal(shape).astype(np.float32))
+    X, DM, Y = f32(N, H, W, C), f32(N, H * W, Kc), f32(N, H * W, Kc)
+    ST, GA, DG, DB = f32(N, 4, 2), f32(Kc), be.empty((Kc,)), be.empty((Kc,))
+    part = be.zeros((be.lib.dyb_groupnorm_bwd_partial_floats(N, H * W, Kc),))
+    wsb = max(be.lib.dyb_conv2d_workspace_bytes(N, H, W, C, Kc, 1, 1, 1, 0), 16)
+    ws = be.empty((wsb // 4,))
+    G0, P00, P10 = _arena(rng, n), _arena(rng, n), _arena(rng, n)
+    G, P0, P1 = be.dev(G0), be.dev(P00), be.dev(P10)
+    before, after = ctypes.c_int(0), ctypes.c_int(0)
+    be.lib.dyb_get_option(b"stat_folds", ctypes.byref(before))
+    check(be.lib.dyb_debug_set_wgrad_update(be.ptr(G), _scope_bytes(n, False), be.ptr(P0), be.ptr(P1), FAST_LR), "set_wgrad_update")
+    try:
+        rc = be.lib.dyb_conv2d_nhwc_wgrad_gn(be.ptr(X), be.ptr(DM), be.ptr(Y), be.ptr(ST), be.ptr(part), be.ptr(GA),
+                                             be.ptr(G) + 4 * ARENA_HEAD, be.ptr(DG), be.ptr(DB), N, H, W, C, Kc, 1, 1, 1, 0, be.ptr(ws), wsb,
+                                             be.stream)
+        be.sync()
+        spans = int(be.lib.dyb_debug_wgrad_update_spans())
+    finally:
+        be.lib.dyb_debug_set_wgrad_update(None, 0, None, None, 0.0)
+    be.lib.dyb_get_option(b"stat_folds", ctypes.byref(after))
+    assert rc == -3, f"expected DYB_ERR_UNSUPPORTED (-3), got {rc}"
+    assert spans == 0, f"{spans} span(s) reported for a launch that never happened"
+    assert after.value == before.value, "stat_folds moved"
+    _assert_arena("p_next", be.host(P1), P10, n)
+    _assert_arena("p_cur", be.host(P0), P00, n)
+    _assert_arena("gradient arena", be.host(G), G0, n)
+
+
 def case_conv_pair(be, N, H, W, C, K, R, stride, pad, seed=0):
     """dyb_debug_conv_pair (the tangent passes' operand pairs: one launch, one K loop over both pairs) against torch:
     forward conv(x1, w1) + conv(x2, w2); data gradient dgrad(dy1, w1) + dgrad(dy2, w2) + addend; weight gradient wgrad(x1, dy1) +

@@ -329,6 +329,12 @@ def test_conv_random_shapes(be, cfg):
     K.case_conv_gn_bwd_fused(be, N, H, W, C, Kc, R, st, pad, relu=1, seed=sum(cfg) + 1)
 
 
+def test_refused_conv_launch_reports_nothing(be):
+    """No report without a launch: a weight gradient refused under an open fast-weight scope pushes no span, bumps no counter and
+    writes nothing (the planner decides before the issuer reports)."""
+    K.case_conv_refusal_reports_nothing(be)
+
+
 def test_conv_is_linear_in_both_operands(be):
     """Size-independent property: conv(a*x1 + x2, w) == a*conv(x1, w) + conv(x2, w), same in w (split-K included)."""
     rng = np.random.default_rng(9)

@@ -102,6 +102,12 @@ def test_conv_inkernel_fold_latency_form_all_resnet_shapes(be, shape):
     assert folds >= 1, shape                         # every shape splits at least one of its three modes at one image
 
 
+def test_refused_conv_launch_reports_nothing(be):
+    """No report without a launch: a weight gradient refused under an open fast-weight scope pushes no span, bumps no counter and
+    writes nothing (the planner decides before the issuer reports)."""
+    K.case_conv_refusal_reports_nothing(be)
+
+
 @pytest.mark.parametrize("tp_grid", [512, 4096])
 @pytest.mark.parametrize("shape", RESNET_SHAPES)
 def test_conv_inkernel_fold_throughput_kernel_all_resnet_shapes(be, throughput_mode, shape, tp_grid):
