@@ -329,6 +329,15 @@ struct Stepper {
   hipEvent_t e_upd = nullptr;
   DybFwdGates gates{};
   bool gates_pending = false;
+  // "wgrad_defer" (round 8; wherever the ranged update applies): a chain backward leaves the weight gradients of layer4 (but block 0's
+  // conv1 / downsample) and of the regressor - HBM streams with a short matrix prologue - behind its join on the auxiliary stream,
+  // where they run beside the NEXT forward's stem .. layer3 instead of beside this backward's GroupNorm backward / data gradients
+  // (DybEvents, hmr_engine.hip backward_body).  The events S.ev->l4 / reg order their readers: the consuming forward
+  // (gates.l4 / reg) or settle_update for every other consumer.  0 = the issue order of round 7 exactly.  Measured at 32 sequences, three
+  // alternating pairs in one session: 493.7 - 495.1 -> 499.8 - 500.9 frames/s (profiles/r08_wgrad_defer_bench.txt).
+  int wgrad_defer = 1;
+  bool defer_pending = false;      // a deferred set has been issued that no consumer has been ordered behind yet
+  int n_deferred = 0;              // launches issued behind a backward's join so far (get_f "deferred_launches": what the tests count)
   int upd_late = 1;                // the last range (layer4 + regressor, 68 % of the parameters) is issued when the forward reaches layer3
   struct LateUpd {                 // what gates.late needs to issue it
     Stepper* S = nullptr;
@@ -477,6 +486,7 @@ extern "C" int dyb_stepper_create(void* plan, int B, int H, int W, void** out) {
   if (const char* e = getenv("DYB_UPD_BLOCKS")) S->upd_blocks = atoi(e);
   if (const char* e = getenv("DYB_SHARE_DYN_FWD")) S->share_dyn_fwd = atoi(e);
   if (const char* e = getenv("DYB_UPD_LATE")) S->upd_late = atoi(e);
+  if (const char* e = getenv("DYB_WGRAD_DEFER")) S->wgrad_defer = atoi(e);
   if (const char* e = getenv("DYB_FUSE_FAST")) S->fuse_fast = atoi(e);
   if (const char* e = getenv("DYB_FUSE_ADAM")) S->fuse_adam = atoi(e);
   if (const char* e = getenv("DYB_FUSE_EMA")) S->fuse_ema = atoi(e);
@@ -488,7 +498,9 @@ extern "C" int dyb_stepper_create(void* plan, int B, int H, int W, void** out) {
       hipEventCreateWithFlags(&S->e_upd, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&S->gates.ev[0], hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&S->gates.ev[1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&S->gates.mid, hipEventDisableTiming) != hipSuccess) {
+      hipEventCreateWithFlags(&S->gates.mid, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&S->ev->l4, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&S->ev->reg, hipEventDisableTiming) != hipSuccess) {
     delete S;
     return DYB_ERR_LAUNCH;
   }
@@ -528,6 +540,7 @@ extern "C" int dyb_stepper_set_i(void* stepper, const char* key, long long v) {
   else if (k == "par_passes") S->par_passes = (int)v;
   else if (k == "par_max_replicas") S->par_max_replicas = (int)v;
   else if (k == "upd_late") S->upd_late = (int)v;
+  else if (k == "wgrad_defer") S->wgrad_defer = (int)v;
   else if (k == "fuse_fast") { DYB_REQUIRE(!S->bound, DYB_ERR_ARG); S->fuse_fast = (int)v; }
   else if (k == "fuse_adam") S->fuse_adam = (int)v;
   else if (k == "fuse_ema") S->fuse_ema = (int)v;
@@ -643,7 +656,7 @@ extern "C" long long dyb_stepper_get_i(const void* stepper, const char* key) {
   return -1;
 }
 // host issue time (ms, accumulated over h_frames frame steps of the frame-loss path) by section:
-// "host_ms_forward", "host_ms_backward", "host_ms_head", "host_ms_update", "host_ms_tail", "host_ms_total", "host_frames"
+// "host_ms_forward", "host_ms_backward", "host_ms_head", "host_ms_update", "host_ms_tail", "host_ms_total", "host_frames"; "deferred_launches"
 extern "C" double dyb_stepper_get_f(const void* stepper, const char* key) {
   const Stepper* S = reinterpret_cast<const Stepper*>(stepper);
   if (!S || !key) return -1.0;
@@ -655,6 +668,7 @@ extern "C" double dyb_stepper_get_f(const void* stepper, const char* key) {
   if (k == "host_ms_tail") return S->h_tail;
   if (k == "host_ms_total") return S->h_total;
   if (k == "host_frames") return (double)S->h_frames;
+  if (k == "deferred_launches") return (double)S->n_deferred;     // "wgrad_defer": launches issued behind a backward's join
   return -1.0;
 }
 extern "C" size_t dyb_stepper_workspace_bytes(void* stepper) {
@@ -733,7 +747,7 @@ static int pass_forward(Stepper& S, Pass& P, const float* theta, const float* im
       return rc;
     }
     // consumed: every range's gate was waited for inside the forward (the deferred one issued there)
-    if (gates) { DYB_REQUIRE(!S.gates.late, DYB_ERR_LAUNCH); S.gates_pending = false; }
+    if (gates) { DYB_REQUIRE(!S.gates.late, DYB_ERR_LAUNCH); S.gates_pending = false; S.defer_pending = false; }
   }
   const float* rot = P.acts + S.off_rot;
   const float* state = P.acts + S.off_state;
@@ -747,6 +761,18 @@ static int pass_frame_head(Stepper& S, Pass& P, const float* kp2d, hipStream_t s
                           (float)S.w2d, (float)S.wshape, (float)S.wpose, P.losses, P.drot_l, P.dshape_l, 10, P.dcam_l, 3, P.djoints_l,
                           S.B, P.lws, (size_t)S.B * 16, st);
 }
+// where a weight update goes by arena ranges (weight_update) - and a chain backward may defer weight gradients ("wgrad_defer")
+static bool ranged_form(const Stepper& S, hipStream_t st, hipStream_t aux) {
+  return S.upd_overlap && S.nrep > 1 && aux && aux != st && S.grp_bounds[0] > 0 && S.grp_bounds[1] > S.grp_bounds[0] &&
+         S.grp_bounds[1] < S.n_params;
+}
+// the engine's backward on the stepper's event set; with "wgrad_defer" in the ranged form it leaves the deferred set in flight on `aux`
+// (never captured: dyb_hmr_backward_ev has no graph cache)
+static int engine_backward(Stepper& S, Pass& P, const float* theta, float* grads, hipStream_t st, hipStream_t aux) {
+  const bool defer = S.wgrad_defer && ranged_form(S, st, aux) && S.ev->l4 && S.ev->reg;
+  if (defer) S.defer_pending = true;           // (also when the call fails half-way: settle_update then waits for what was issued)
+  return dyb_hmr_backward_ev(S.plan, theta, P.acts, P.d_rot, P.d_state, S.n_iter, grads, P.ws, S.ws_bytes, st, aux, S.ev, defer, &S.n_deferred);
+}
 // gradient of the pass's loss total w.r.t. `theta` into `grads` (the same five C calls as fused_level._LevelFunction.backward)
 static int pass_backward(Stepper& S, Pass& P, const float* theta, float* grads, hipStream_t st, hipStream_t aux) {
   RUN(dyb_scale_add(nullptr, P.djoints_l, nullptr, P.djoints, (size_t)S.B * NJ * 3, st));
@@ -754,7 +780,7 @@ static int pass_backward(Stepper& S, Pass& P, const float* theta, float* grads, 
                   S.lbs_wsb, st));
   RUN(dyb_head_grad_combine(nullptr, P.drot_l, P.drot_s, nullptr, P.dshape_l, P.dbetas_s, nullptr, P.dcam_l, nullptr, P.d_rot,
                             P.d_state, S.B, st));
-  return dyb_hmr_backward_ev(S.plan, theta, P.acts, P.d_rot, P.d_state, S.n_iter, grads, P.ws, S.ws_bytes, st, aux, S.ev);
+  return engine_backward(S, P, theta, grads, st, aux);
 }
 // ground-truth side of the metrics (depends on the batch only): male / female / neutral meshes from the axis-angle pose
 static int gt_meshes(Stepper& S, const float* gt_pose, const float* gt_betas, hipStream_t st) {
@@ -1009,9 +1035,20 @@ static int weight_update(Stepper& S, bool adam, const float* p, float* out, hipS
     }
     return fastweight_range(S, p, out, g2, g3, lo, hi, s);
   };
-  const bool ranged = S.upd_overlap && S.nrep > 1 && aux && aux != st && S.grp_bounds[0] > 0 && S.grp_bounds[1] > S.grp_bounds[0] &&
-                      S.grp_bounds[1] < S.n_params;
-  if (!ranged) return range(0, S.n_params, st);
+  const bool ranged = ranged_form(S, st, aux);
+  if (!ranged) {
+    if (S.defer_pending) {         // (a switch flipped between the backward and its update) the pass reads / rewrites what the deferred set writes
+      HIPOK(hipStreamWaitEvent(st, S.ev->l4, 0));
+      HIPOK(hipStreamWaitEvent(st, S.ev->reg, 0));
+      S.defer_pending = false;
+    }
+    return range(0, S.n_params, st);
+  }
+  // the consuming forward waits for the level's deferred weight gradients too.  The ranged pass of [layer4, end) below / in late_update
+  // writes the spans of that arena range those launches did NOT update themselves (and, without fused epilogues, reads their gradients):
+  // it is issued on `aux`, an in-order stream, behind them - keep it there.
+  S.gates.l4 = S.defer_pending ? S.ev->l4 : nullptr;
+  S.gates.reg = S.defer_pending ? S.ev->reg : nullptr;
   RUN(range(0, S.grp_bounds[0], st));
   HIPOK(hipEventRecord(S.e_upd, st));                 // the gradients' main-stream writers (and the first range) are behind this point
   HIPOK(hipStreamWaitEvent(aux, S.e_upd, 0));
@@ -1037,6 +1074,11 @@ static int weight_update(Stepper& S, bool adam, const float* p, float* out, hipS
 }
 // make `st` wait for a ranged update nobody has consumed yet (a consumer other than a forward follows)
 static int settle_update(Stepper& S, hipStream_t st) {
+  if (S.defer_pending && !S.gates_pending) {         // a backward deferred weight gradients and no update followed it (it failed half-way)
+    HIPOK(hipStreamWaitEvent(st, S.ev->l4, 0));
+    HIPOK(hipStreamWaitEvent(st, S.ev->reg, 0));
+    S.defer_pending = false;
+  }
   if (!S.gates_pending) return DYB_OK;
   if (S.gates.late) {                               // nobody's forward will call it: issue the deferred range now
     HIPOK(hipEventRecord(S.gates.mid, st));
@@ -1044,6 +1086,11 @@ static int settle_update(Stepper& S, hipStream_t st) {
   }
   HIPOK(hipStreamWaitEvent(st, S.gates.ev[0], 0));
   HIPOK(hipStreamWaitEvent(st, S.gates.ev[1], 0));
+  if (S.defer_pending) {                            // the deferred weight gradients of the level this update belongs to
+    HIPOK(hipStreamWaitEvent(st, S.ev->l4, 0));
+    HIPOK(hipStreamWaitEvent(st, S.ev->reg, 0));
+    S.defer_pending = false;
+  }
   S.gates_pending = false;
   return DYB_OK;
 }
@@ -1162,7 +1209,7 @@ static int pass_backward_ext(Stepper& S, Pass& P, const float* theta, float* gra
   const float* z = S.zeros;
   RUN(dyb_head_grad_combine(nullptr, frame_loss ? P.drot_l : z, P.drot_s, e_rot, frame_loss ? P.dshape_l : z, P.dbetas_s, e_shape,
                             frame_loss ? P.dcam_l : z, e_cam, P.d_rot, P.d_state, S.B, st));
-  return dyb_hmr_backward_ev(S.plan, theta, P.acts, P.d_rot, P.d_state, S.n_iter, grads, P.ws, S.ws_bytes, st, aux, S.ev);
+  return engine_backward(S, P, theta, grads, st, aux);
 }
 enum { IN_IMAGE = 0, IN_KP, IN_GT_POSE, IN_GT_BETAS, IN_GENDER, IN_HIST_IMAGE, IN_HIST_KP, IN_EX_IMG, IN_EX_KP, IN_EX_POSE,
        IN_EX_BETAS, IN_EX_POSE3D, IN_COUNT };
@@ -1233,6 +1280,10 @@ static int full_level(Stepper& S, FullCtx& C, Pass& P, const float* cur, bool up
     for (int k = 0; k < 2; ++k) {
       if (motion) HIPOK(hipStreamWaitEvent(sB, S.gates.ev[k], 0));
       if (label) HIPOK(hipStreamWaitEvent(sC, S.gates.ev[k], 0));
+    }
+    for (hipEvent_t e : {S.gates.l4, S.gates.reg}) {     // ... and for the deferred weight gradients that wrote layer4 / the regressor
+      if (e && motion) HIPOK(hipStreamWaitEvent(sB, e, 0));
+      if (e && label) HIPOK(hipStreamWaitEvent(sC, e, 0));
     }
   }
   if (par && motion) {
@@ -1653,6 +1704,8 @@ extern "C" int dyb_stepper_join(void* stepper, hipStream_t st) {
   DYB_REQUIRE(S, DYB_ERR_ARG);
   RUN(side_wait(*S));
   if ((S->tail.on || S->gtjob.on) && S->tail_stream) RUN(issue_side_work(*S, S->tail_stream));      // the last frame's final inference
+  // (every frame step ends with a forward that consumed them; only a step that failed after its backward leaves deferred weight gradients behind)
+  if (S->defer_pending && !S->gates_pending) RUN(settle_update(*S, st));
   if (S->side_pending) {
     HIPOK(hipStreamWaitEvent(st, S->e_side, 0));
     S->side_pending = false;

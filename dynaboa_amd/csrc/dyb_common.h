@@ -320,6 +320,12 @@ int dyb_avgpool_fwd_tail(const float* x, float* const* dsts, int ndst, int ld, i
 struct DybEvents {
   std::vector<hipEvent_t> dy;
   hipEvent_t join = nullptr;
+  // Deferred weight gradients (the frame stepper's "wgrad_defer"; both events are the caller's, the plan's own set has none): asked
+  // to defer (dyb_hmr_backward_ev), a two-stream backward issues the weight gradients of layer4 (all but block 0's conv1 /
+  // downsample) and of the regressor on the auxiliary stream BEHIND `join` - the chain's stream no longer waits for them - and
+  // records `l4` after the convolutions, `reg` after the regressor's.  Whoever reads those weights / rewrites those layers'
+  // activations waits for them.
+  hipEvent_t l4 = nullptr, reg = nullptr;
 };
 DybEvents* dyb_hmr_events_create(const void* plan);
 void dyb_hmr_events_destroy(DybEvents* e);
@@ -335,9 +341,14 @@ struct DybFwdGates {
   hipEvent_t mid = nullptr;
   int (*late)(void* user) = nullptr;
   void* user = nullptr;
+  // optional: the previous backward's deferred weight gradients (DybEvents::l4 / reg).  They read layer4's / the regressor's saved
+  // activations and write those weights: waited for where ev[1] is (before layer4's first block) and before the pooled feature
+  // (the first regressor activation the forward rewrites)
+  hipEvent_t l4 = nullptr, reg = nullptr;
 };
 void dyb_hmr_param_groups(const void* plan, size_t bounds[2]);
 int dyb_hmr_forward_plain(void* plan, const float* params, const float* image, const float* init_state, int n_iter, float* acts,
                           void* ws, size_t ws_bytes, hipStream_t st, const DybFwdGates* gates = nullptr);
 int dyb_hmr_backward_ev(void* plan, const float* params, const float* acts, const float* d_rotmat, const float* d_state,
-                        int n_iter, float* grads, void* ws, size_t ws_bytes, hipStream_t st, hipStream_t aux, const DybEvents* ev);
+                        int n_iter, float* grads, void* ws, size_t ws_bytes, hipStream_t st, hipStream_t aux, const DybEvents* ev,
+                        bool defer = false, int* n_deferred = nullptr);      // defer: see DybEvents; *n_deferred += launches issued behind the join

@@ -312,6 +312,8 @@ void dyb_hmr_events_destroy(DybEvents* e) {
   if (!e) return;
   for (hipEvent_t x : e->dy) (void)hipEventDestroy(x);
   (void)hipEventDestroy(e->join);
+  if (e->l4) (void)hipEventDestroy(e->l4);
+  if (e->reg) (void)hipEventDestroy(e->reg);
   delete e;
 }
 extern "C" size_t dyb_hmr_param_floats(const void* plan) { return reinterpret_cast<const HmrPlan*>(plan)->n_params; }
@@ -581,7 +583,11 @@ static int forward_body(const HmrPlan& P, const float* params, const float* init
           RUN(gates->late(gates->user));
         }
       }
-      if (bi == P.layer_last_block[2] + 1 && gates->ev[1] && hipStreamWaitEvent(st, gates->ev[1], 0) != hipSuccess) return DYB_ERR_LAUNCH;
+      if (bi == P.layer_last_block[2] + 1) {
+        if (gates->ev[1] && hipStreamWaitEvent(st, gates->ev[1], 0) != hipSuccess) return DYB_ERR_LAUNCH;
+        // the previous backward's deferred layer4 weight gradients still read layer4's activations and write its weights
+        if (gates->l4 && hipStreamWaitEvent(st, gates->l4, 0) != hipSuccess) return DYB_ERR_LAUNCH;
+      }
     }
     // 3 launches per conv become 2 (or 1: the small 1x1 layers write their statistics themselves): bn1 / bn2 (+ReLU)
     // are applied by conv2 / conv3 while loading
@@ -603,6 +609,8 @@ static int forward_body(const HmrPlan& P, const float* params, const float* init
   }
   float* dsts[MAX_ITER];
   for (int t = 0; t < n_iter; ++t) dsts[t] = acts + P.a_xc[t];
+  // (the previous backward's deferred regressor weight gradients read xc / h1 / h2 and write fc1 / fc2 / the decoder)
+  if (gates && gates->reg && hipStreamWaitEvent(st, gates->reg, 0) != hipSuccess) return DYB_ERR_LAUNCH;
   RUN(dyb_avgpool_fwd_tail(x, dsts, n_iter, FC1_IN_PAD, B, P.featHW, FEAT, init_state, STATE_LD, STATE_LD, FEAT, st));
   // fc1 over xc = [pooled feature (2048) | state (157)]: the feature is the same in every iteration, so its 93 % of the weight
   // matrix is streamed ONCE per forward (pre = b + W[:, :2048] feat) and each iteration adds the state columns' product
@@ -729,10 +737,15 @@ static int layer_gn_bwd(HmrPlan& P, int ci, const float* params, const float* ac
   *dm_out = dm;
   return DYB_OK;
 }
+// (`held`: jobs of `deferrable` layers in the throughput form are kept for the end of the call instead)
 static int flush_wgrads(HmrPlan& P, std::vector<WgradJob>& jobs, hipEvent_t done, const float* params, const float* acts,
-                        float* grads, const WsCarve& w, hipStream_t aux) {
+                        float* grads, const WsCarve& w, hipStream_t aux, const std::vector<char>& deferrable,
+                        std::vector<WgradJob>& held) {
   if (hipStreamWaitEvent(aux, done, 0) != hipSuccess) return DYB_ERR_LAUNCH;
-  for (const WgradJob& j : jobs) RUN(run_wgrad(P, j, params, acts, grads, w, w.conv_aux, aux));
+  for (const WgradJob& j : jobs) {
+    if (deferrable[j.ci] && j.dy) held.push_back(j);
+    else RUN(run_wgrad(P, j, params, acts, grads, w, w.conv_aux, aux));
+  }
   jobs.clear();
   return DYB_OK;
 }
@@ -783,12 +796,13 @@ static int layer_dgrad_k4(HmrPlan& P, int ci, int pi, const float* params, const
 // returns with `stream` already waiting for them, so callers keep ordering on `stream` only.
 static int backward_body(HmrPlan& P, const float* params, const float* acts, const float* d_rotmat, const float* d_state,
                          int n_iter, float* grads, const WsCarve& w, hipStream_t st, hipStream_t aux, const DybEvents& E,
-                         const DropCfg& drop = kNoDrop);
+                         const DropCfg& drop = kNoDrop, bool defer_req = false, int* n_deferred = nullptr);
 
 // the same call with the caller's own event set and no graph cache: what the native frame stepper issues (several chains
 // of one plan may be in flight on different streams, each with its own workspace and events)
 int dyb_hmr_backward_ev(void* plan, const float* params, const float* acts, const float* d_rotmat, const float* d_state,
-                        int n_iter, float* grads, void* ws, size_t ws_bytes, hipStream_t st, hipStream_t aux, const DybEvents* ev) {
+                        int n_iter, float* grads, void* ws, size_t ws_bytes, hipStream_t st, hipStream_t aux, const DybEvents* ev,
+                        bool defer, int* n_deferred) {
   HmrPlan* Pp = reinterpret_cast<HmrPlan*>(plan);
   DYB_REQUIRE(Pp && params && acts && d_rotmat && d_state && grads && ws, DYB_ERR_ARG);
   DYB_REQUIRE(n_iter >= 1 && n_iter <= MAX_ITER, DYB_ERR_UNSUPPORTED);
@@ -796,7 +810,7 @@ int dyb_hmr_backward_ev(void* plan, const float* params, const float* acts, cons
   if (aux == st || !ev) aux = nullptr;
   WsCarve w = carve(*Pp, ws);
   static const DybEvents none;
-  return backward_body(*Pp, params, acts, d_rotmat, d_state, n_iter, grads, w, st, aux, ev ? *ev : none);
+  return backward_body(*Pp, params, acts, d_rotmat, d_state, n_iter, grads, w, st, aux, ev ? *ev : none, kNoDrop, defer, n_deferred);
 }
 // forward without the graph cache (same reason)
 void dyb_hmr_param_groups(const void* plan, size_t bounds[2]) {
@@ -862,7 +876,7 @@ extern "C" int dyb_hmr_backward(void* plan, const float* params, const float* ac
 
 static int backward_body(HmrPlan& P, const float* params, const float* acts, const float* d_rotmat, const float* d_state,
                          int n_iter, float* grads, const WsCarve& w, hipStream_t st, hipStream_t aux, const DybEvents& E,
-                         const DropCfg& drop) {
+                         const DropCfg& drop, bool defer_req, int* n_deferred) {
   DybBf16Scope bf(P.bf16 != 0);
   const int B = P.B;
   float* d_st[MAX_ITER + 1];
@@ -900,16 +914,36 @@ static int backward_body(HmrPlan& P, const float* params, const float* acts, con
     RUN(dyb_linear_bwd_dx(dsum, HID, params + P.fc1_w, FC1_IN_PAD, B, FEAT, HID, d_xf, FC1_IN_PAD, 0, FEAT, nullptr, 0, nullptr, 0, w.lin,
                           P.ws_lin, st));
   }
-  {
+  // the regressor's weight gradients (fc1 / fc2 / decoder, the scope's weight update in their epilogue): HBM streams that depend on
+  // nothing in the backbone backward - in line here, or with the deferred set at the end of the call
+  auto regressor_dw = [&](hipStream_t s) -> int {
     const float *dys[MAX_ITER], *xs[MAX_ITER];
     int ldd[MAX_ITER], ldx[MAX_ITER];
     for (int t = 0; t < n_iter; ++t) { dys[t] = d_st[t + 1]; ldd[t] = STATE_LD; xs[t] = acts + (drop.on ? P.a_h2d[t] : P.a_h2[t]); ldx[t] = HID; }
-    RUN(dyb_linear_bwd_dw(dys, ldd, xs, ldx, n_iter, B, HID, STATE_LD, grads + P.dec_w, HID, grads + P.dec_b, st));
+    RUN(dyb_linear_bwd_dw(dys, ldd, xs, ldx, n_iter, B, HID, STATE_LD, grads + P.dec_w, HID, grads + P.dec_b, s));
     for (int t = 0; t < n_iter; ++t) { dys[t] = d_h2[t]; ldd[t] = HID; xs[t] = acts + (drop.on ? P.a_h1d[t] : P.a_h1[t]); ldx[t] = HID; }
-    RUN(dyb_linear_bwd_dw(dys, ldd, xs, ldx, n_iter, B, HID, HID, grads + P.fc2_w, HID, grads + P.fc2_b, st));
+    RUN(dyb_linear_bwd_dw(dys, ldd, xs, ldx, n_iter, B, HID, HID, grads + P.fc2_w, HID, grads + P.fc2_b, s));
     for (int t = 0; t < n_iter; ++t) { dys[t] = d_h1[t]; ldd[t] = HID; xs[t] = acts + P.a_xc[t]; ldx[t] = FC1_IN_PAD; }
-    RUN(dyb_linear_bwd_dw(dys, ldd, xs, ldx, n_iter, B, FC1_IN_PAD, HID, grads + P.fc1_w, FC1_IN_PAD, grads + P.fc1_b, st));
+    return dyb_linear_bwd_dw(dys, ldd, xs, ldx, n_iter, B, FC1_IN_PAD, HID, grads + P.fc1_w, FC1_IN_PAD, grads + P.fc1_b, s);
+  };
+  // Deferred weight gradients (`defer_req`; DybEvents, dyb_common.h): the layers whose EVERY input the next forward rewrites only behind its
+  // layer4 gate - layer4's convolutions except block 0's conv1 / downsample (those two read layer3's last output, which the next
+  // forward rewrites before it reaches the gate: they stay in the backward rather than pulling the forward's wait up in front of
+  // layer3's last GroupNorm apply, where it would stall the forward on the whole auxiliary queue) - and the regressor.  Only the
+  // throughput form qualifies (the layer's dy materialised in its own w.dy2 slot); a forward touches neither w.dy2, w.reg, the
+  // auxiliary slab region nor the auxiliary counter region.
+  const bool defer = aux && defer_req && E.l4 && E.reg && !drop.on;
+  std::vector<char> deferrable(P.convs.size(), 0);
+  if (defer) {
+    const int first4 = P.layer_last_block[2] + 1;
+    for (int bi = first4; bi < (int)P.blocks.size(); ++bi) {
+      const BlockL& b = P.blocks[bi];
+      deferrable[b.c2] = deferrable[b.c3] = 1;
+      if (bi > first4) deferrable[b.c1] = 1;
+    }
   }
+  std::vector<WgradJob> deferred;
+  if (!defer) RUN(regressor_dw(st));
 
   // ---- backbone, last block first.  D0/D1 ping-pong the data gradients travelling down the main
   // branch, Rb holds the shortcut branch's data gradient; the residual-edge gradient of a block is the
@@ -961,12 +995,12 @@ static int backward_body(HmrPlan& P, const float* params, const float* acts, con
       RUN(layer_gn_bwd(P, b.c1, params, acts, grads, xin, nullptr, p2, 1, &dm1, w, st, jobs, nullptr, false));
       // shortcut branch: GroupNorm without ReLU on the residual-edge gradient; its data gradient is materialised
       RUN(layer_gn_bwd(P, b.cd, params, acts, grads, xin, nullptr, plain(dm3), 0, &dmd, w, st, jobs, ev, false));
-      if (aux) RUN(flush_wgrads(P, jobs_store, ev, params, acts, grads, w, aux));
+      if (aux) RUN(flush_wgrads(P, jobs_store, ev, params, acts, grads, w, aux, deferrable, deferred));
       RUN(layer_dgrad(P, b.cd, params, acts, dmd, Rb, nullptr, nullptr, w, st, bs));
       edge = Rb;
     } else {
       RUN(layer_gn_bwd(P, b.c1, params, acts, grads, xin, nullptr, p2, 1, &dm1, w, st, jobs, ev, false));
-      if (aux) RUN(flush_wgrads(P, jobs_store, ev, params, acts, grads, w, aux));
+      if (aux) RUN(flush_wgrads(P, jobs_store, ev, params, acts, grads, w, aux, deferrable, deferred));
     }
     k4 = false;
     if (bi > 0) {
@@ -992,10 +1026,20 @@ static int backward_body(HmrPlan& P, const float* params, const float* acts, con
   const float* dm0;
   RUN(layer_gn_bwd(P, 0, params, acts, grads, acts + P.a_x4, nullptr, plain(spare), 1, &dm0, w, st, jobs,
                    aux ? E.dy[0] : nullptr, false));
-  if (aux) RUN(flush_wgrads(P, jobs_store, E.dy[0], params, acts, grads, w, aux));
+  if (aux) RUN(flush_wgrads(P, jobs_store, E.dy[0], params, acts, grads, w, aux, deferrable, deferred));
   if (aux) {
     if (hipEventRecord(E.join, aux) != hipSuccess) return DYB_ERR_LAUNCH;
     if (hipStreamWaitEvent(st, E.join, 0) != hipSuccess) return DYB_ERR_LAUNCH;
+    if (defer) {
+      // behind the join: the chain's stream does not wait for these.  The auxiliary stream has waited for every per-block event of
+      // this call (the last one, the stem's, was recorded on `st` behind the regressor's data gradients and every layer4 reduce).
+      // Issued inside the call: the weight-update scope of the calling thread still holds, and its span list is complete on return.
+      for (const WgradJob& j : deferred) RUN(run_wgrad(P, j, params, acts, grads, w, w.conv_aux, aux));
+      if (hipEventRecord(E.l4, aux) != hipSuccess) return DYB_ERR_LAUNCH;
+      RUN(regressor_dw(aux));
+      if (hipEventRecord(E.reg, aux) != hipSuccess) return DYB_ERR_LAUNCH;
+      if (n_deferred) *n_deferred += (int)deferred.size() + 3;
+    }
   }
   return DYB_OK;
 }
