@@ -426,5 +426,55 @@ class BaseAdaptor:
     def inference(self, batch, model, need_feature=False):
         pass
 
+    # ------------------------------------------------------------------ rendered results (--save_res 1)
+    RESULT_COLOR = (205 / 255.0, 129 / 255.0, 98 / 255.0)          # reference base_adaptor.py:442
+
+    def _renderer(self, width, height):
+        from .render import Renderer
+        cache = self.__dict__.setdefault("_renderers", {})
+        key = (int(width), int(height))
+        if key not in cache:
+            cache.clear()                                            # frames of one stream share a size: keep one
+            cache[key] = Renderer(resolution=key, orig_img=True, wireframe=False, faces=self.smpl_neutral.faces, device=self.device)
+        return cache[key]
+
+    def save_results(self, vts, cam, images, name, bbox, prefix=None):
+        """reference base_adaptor.py:429-443: the predicted mesh drawn over its frame, one PNG per frame of the batch at
+        ``exppath/image/{prefix}_{global_step + i}.png``.  vts (B, 6890, 3), cam (B, 3) = (s, tx, ty) of the crop, images the
+        normalised (B, 3, 224, 224) crops, name / bbox the batch's ``imgname`` / ``bbox`` (cx, cy, h) - both None for a stream
+        without image files (the synthetic bundle): the mesh is then drawn over the de-normalised crop with the crop's own camera
+        (s, s, tx, ty).  Vertices, camera and frame stay on the device; only the finished picture comes to the host.
+        -> the written paths."""
+        from PIL import Image
+        from .render import convert_crop_cam_to_orig_img
+        vts, cam = vts.detach(), cam.detach().float()
+        outdir = os.path.join(self.exppath, "image")
+        os.makedirs(outdir, exist_ok=True)
+        B = vts.shape[0]
+        paths = [os.path.join(outdir, f"{prefix}_{self.global_step + i}.png") for i in range(B)]
+        imgdir = getattr(self, "imgdir", None)
+        files = [os.path.join(imgdir, n) for n in name] if (name is not None and bbox is not None and imgdir is not None) else None
+        if files is not None and all(os.path.isfile(f) for f in files):
+            from .datasets import read_image
+            bbox = bbox.detach().to(cam.device).float()
+            for i, f in enumerate(files):
+                frame = torch.from_numpy(read_image(f)).to(self.device)
+                h, w = int(frame.shape[0]), int(frame.shape[1])
+                ocam = convert_crop_cam_to_orig_img(cam[i:i + 1], bbox[i:i + 1], w, h)
+                pic = self._renderer(w, h).render(frame, vts[i], ocam[0], color=self.RESULT_COLOR)
+                Image.fromarray(pic.cpu().numpy()).save(paths[i])
+            return paths
+        mean = torch.tensor(constants.IMG_NORM_MEAN, device=images.device).view(1, 3, 1, 1)
+        std = torch.tensor(constants.IMG_NORM_STD, device=images.device).view(1, 3, 1, 1)
+        crops = ((images.detach() * std + mean) * 255.0).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+        ccam = torch.stack([cam[:, 0], cam[:, 0], cam[:, 1], cam[:, 2]], 1)
+        res = int(images.shape[-1])
+        for lo in range(0, B, 64):                                   # one launch draws up to 64 meshes
+            hi = min(lo + 64, B)
+            pics = self._renderer(res, res).render(crops[lo:hi], vts[lo:hi], ccam[lo:hi], color=self.RESULT_COLOR).cpu().numpy()
+            for i in range(lo, hi):
+                Image.fromarray(pics[i - lo]).save(paths[i])
+        return paths
+
     def write_summaries(self, losses):
         self.last_summaries = losses

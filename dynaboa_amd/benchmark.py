@@ -557,6 +557,12 @@ class Adaptor(BaseAdaptor):
             joblib.dump({'verts': pred_vertices.cpu().numpy(), 'cam': cam_t.cpu().numpy(),
                          'rotmat': pred_rotmat.cpu().numpy(), 'beta': pred_shape.cpu().numpy()},
                         os.path.join(self.exppath, 'result', f'Pred_{self.global_step}.pt'))
+        if getattr(self.options, "save_res", 0) and (tag is None or tag[0] == 'final'):
+            # reference dynaboa_benchmark.py:257-258 (its call passes two arguments too many and would raise; the method's own
+            # signature is used).  There every inference() of a frame writes Pred_{step}.png and the last one's file stays; here
+            # only the inference() behind an optimiser step ('final'; no tag: a caller of its own) draws - the lower-level
+            # evaluations of the same frame would only be overwritten
+            self.save_results(pred_vertices, pred_cam, image, batch.get('imgname'), batch.get('bbox'), prefix='Pred')
         if self.options.deferred_metrics:
             self._pending.append(dict(step=step, tag=tag, pred=pred14, gt=gt14, mpjpe=mpjpe_t, pve=pve_t))
             res = (mpjpe_t, None, pve_t)

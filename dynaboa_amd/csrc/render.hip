@@ -1,0 +1,324 @@
+// Mesh overlay on the device: a deterministic triangle rasteriser that draws N meshes (one per sequence of a step) over their
+// frames in one call.  It stands where the reference draws one frame at a time through pyrender on OpenGL and the host
+// (render_demo.py:58-134 as called from base_adaptor.py:429-443): the mesh turned 180 degrees about X, a weak-perspective
+// camera (sx, sy, tx, ty), three point lights, one opaque colour, the picture pasted over the frame where the mesh covers it.
+//
+// Conventions (tests/render_ref.py restates them in numpy; the two agree bit for bit on coverage):
+//   image position   u = W/2 (1 + sx (X + tx)),  v = H/2 (1 + sy (Y + ty))   fp32, one rounding per operation (no fused
+//                    multiply-add: contraction is switched off for this file), pixel centres at (i + 0.5, j + 0.5);
+//                    depth is the model's Z, smaller = nearer; no near / far plane.
+//   coverage         u, v snapped to 1/256 pixel (round to nearest even), int64 edge functions, top-left fill rule: a pixel
+//                    centre on an edge shared by two faces belongs to exactly one of them.  A face is drawn when its snapped
+//                    area is > 0 in the orientation where the model-space normal (v1 - v0) x (v2 - v0) has negative Z (back faces
+//                    and degenerate faces drop out, as for pyrender's single-sided material).  A face with a snapped coordinate
+//                    beyond 2^30 (4 million pixels from the origin) or not finite, or with a corner whose Z is not finite, is
+//                    dropped: inside that range the int64 edge functions (differences below 2^32, widened before they are
+//                    formed, products below 2^64 / 4) cannot overflow whatever the frame size.
+//   depth            (w0 z0 + w1 z1 + w2 z2) / area with the integer weights converted to fp32; nearest wins, ties go to the
+//                    lower face index.  Every pixel is owned by one thread which sees every face: no atomics on the result,
+//                    nothing depends on the order workgroups or threads run in.
+//   shading          smooth: vertex normal = normalised sum of the unnormalised normals of the incident faces, gathered in
+//                    the order of the vertex -> face CSR table (deterministic, unlike a scatter of float atomics); normal and
+//                    position barycentric per pixel, normal renormalised; in the turned space p' = (X, -Y, -Z):
+//                    I = min(1, 0.3 + 0.35 sum_k max(0, n' . dir(L_k - p'))), L = (0,-1,1), (0,1,1), (1,1,2), no falloff;
+//                    pixel = round(255 I colour).  This is NOT pyrender's metallic-roughness shading (unpinned: pyrender is
+//                    absent from the build image); geometry, visibility and the light set-up are the reference's.
+//
+// Three kernels: vertex normals (one thread per vertex), face set-up (one thread per face: snapped corners + pixel box, an empty
+// box for culled / off-image faces), and one workgroup per 16x16 pixel tile that streams the face boxes 256 at a time, compacts
+// the faces touching the tile into LDS (with their corners and depths) and lets each thread keep the nearest face of its pixel.
+// The list is processed chunk by chunk, so no per-tile capacity can overflow (the synthetic SMPL's random-triple faces put
+// thousands of faces over one tile).
+#include "dyb_common.h"
+
+#pragma clang fp contract(off)
+
+#define RND_TILE 16
+#define RND_CHUNK 256
+#define RND_MAX_N 64
+#define RND_MAX_DIM 4096
+#define RND_EMPTY_BOX 0x0000ffff                 // lo = 65535 > every pixel index, hi = 0
+#define RND_SNAP_LIMIT 1073741824.0f             // 2^30 in 1/256-pixel units
+
+typedef unsigned rnd_u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ int rnd_min(int a, int b) { return a < b ? a : b; }
+__device__ __forceinline__ int rnd_max(int a, int b) { return a > b ? a : b; }
+static inline size_t rnd_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// ---- vertex normals ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void render_vnormal_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                             const int* __restrict__ adj_ptr, const int* __restrict__ adj_idx, int V,
+                                                             int F, float* __restrict__ vnorm) {
+  const int v = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
+  if (v >= V) return;
+  const float* P = verts + (size_t)n * V * 3;
+  float sx = 0.f, sy = 0.f, sz = 0.f;
+  int lo = adj_ptr[v], hi = adj_ptr[v + 1];
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > 3 * F ? 3 * F : hi;
+  for (int k = lo; k < hi; ++k) {
+    const int f = adj_idx[k];
+    if ((unsigned)f >= (unsigned)F) continue;
+    const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+    if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) continue;
+    const float ax = P[3 * i1] - P[3 * i0], ay = P[3 * i1 + 1] - P[3 * i0 + 1], az = P[3 * i1 + 2] - P[3 * i0 + 2];
+    const float bx = P[3 * i2] - P[3 * i0], by = P[3 * i2 + 1] - P[3 * i0 + 1], bz = P[3 * i2 + 2] - P[3 * i0 + 2];
+    sx += ay * bz - az * by;
+    sy += az * bx - ax * bz;
+    sz += ax * by - ay * bx;
+  }
+  const float len = sqrtf(sx * sx + sy * sy + sz * sz);
+  const float inv = len > 0.f ? 1.f / len : 0.f;
+  float* o = vnorm + ((size_t)n * V + v) * 3;
+  o[0] = sx * inv;
+  o[1] = sy * inv;
+  o[2] = sz * inv;
+}
+
+// ---- face set-up ---------------------------------------------------------------------------------------------------------------
+// snapped image position of a vertex; false when it leaves the range the int64 edge functions are safe in
+__device__ __forceinline__ bool render_snap(const float* p, float hw, float hh, float sx, float sy, float tx, float ty, int& u, int& v) {
+  const float fu = rintf(hw * (1.f + sx * (p[0] + tx)) * 256.f);
+  const float fv = rintf(hh * (1.f + sy * (p[1] + ty)) * 256.f);
+  // false for NaN as well; a corner whose depth is not finite drops its faces too, so that every depth compared below is ordered
+  const bool ok = fabsf(fu) <= RND_SNAP_LIMIT && fabsf(fv) <= RND_SNAP_LIMIT && fabsf(p[2]) < __uint_as_float(0x7f800000u);
+  u = ok ? (int)fu : 0;
+  v = ok ? (int)fv : 0;
+  return ok;
+}
+// The drawn orientation: corners (a, b, c) = (v0, v2, v1), so that a front face has a positive area below.
+__device__ __forceinline__ long long render_edge(int ax, int ay, int bx, int by, int px, int py) {
+  // widened before the subtraction: two corners at +-2^30 differ by 2^31
+  return ((long long)bx - ax) * ((long long)py - ay) - ((long long)by - ay) * ((long long)px - ax);
+}
+// top-left rule for the edge a -> b of a positively oriented triangle (x right, y down): a pixel centre ON the edge is inside
+// when the edge is a left edge (it runs upwards) or a top edge (horizontal, running right)
+__device__ __forceinline__ bool render_owns_edge(int ax, int ay, int bx, int by) { return by < ay || (by == ay && bx > ax); }
+
+__global__ __launch_bounds__(256) void render_face_setup_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                                const float* __restrict__ cam, int V, int F, int H, int W,
+                                                                int* __restrict__ fcoord, int* __restrict__ fbox) {
+  const int f = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
+  if (f >= F) return;
+  const float* P = verts + (size_t)n * V * 3;
+  const float sx = cam[4 * n], sy = cam[4 * n + 1], tx = cam[4 * n + 2], ty = cam[4 * n + 3];
+  const float hw = 0.5f * (float)W, hh = 0.5f * (float)H;
+  const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+  int x0 = 0, y0 = 0, x1 = 0, y1 = 0, x2 = 0, y2 = 0;
+  bool ok = (unsigned)i0 < (unsigned)V && (unsigned)i1 < (unsigned)V && (unsigned)i2 < (unsigned)V;
+  if (ok) {
+    ok = render_snap(P + 3 * i0, hw, hh, sx, sy, tx, ty, x0, y0);
+    ok = render_snap(P + 3 * i1, hw, hh, sx, sy, tx, ty, x1, y1) && ok;
+    ok = render_snap(P + 3 * i2, hw, hh, sx, sy, tx, ty, x2, y2) && ok;
+  }
+  int bx = RND_EMPTY_BOX, by = RND_EMPTY_BOX;
+  if (ok && render_edge(x0, y0, x2, y2, x1, y1) > 0) {
+    const int xmin = rnd_min(x0, rnd_min(x1, x2)), xmax = rnd_max(x0, rnd_max(x1, x2));
+    const int ymin = rnd_min(y0, rnd_min(y1, y2)), ymax = rnd_max(y0, rnd_max(y1, y2));
+    // pixel i has its centre at 256 i + 128: the pixels whose centre lies in [min, max]
+    int ilo = (xmin + 127) >> 8, ihi = (xmax - 128) >> 8, jlo = (ymin + 127) >> 8, jhi = (ymax - 128) >> 8;
+    ilo = rnd_max(ilo, 0);
+    ihi = rnd_min(ihi, W - 1);
+    jlo = rnd_max(jlo, 0);
+    jhi = rnd_min(jhi, H - 1);
+    if (ilo <= ihi && jlo <= jhi) {
+      bx = ilo | (ihi << 16);
+      by = jlo | (jhi << 16);
+    }
+  }
+  const size_t g = (size_t)n * F + f;
+  int* c = fcoord + g * 6;
+  c[0] = x0; c[1] = y0; c[2] = x1; c[3] = y1; c[4] = x2; c[5] = y2;
+  fbox[2 * g] = bx;
+  fbox[2 * g + 1] = by;
+}
+
+// ---- one workgroup per 16x16 tile ----------------------------------------------------------------------------------------------
+struct RenderHit {
+  long long wa, wb, wc, area;      // weights of v0, v2, v1 (the drawn orientation) and their sum
+};
+// coverage of the pixel centre (px, py), in snapped units, by the face with corners v0 = (x0, y0), v1, v2
+__device__ __forceinline__ bool render_cover(int x0, int y0, int x1, int y1, int x2, int y2, int px, int py, RenderHit& h) {
+  // a = v0, b = v2, c = v1
+  h.wa = render_edge(x2, y2, x1, y1, px, py);      // edge b -> c, weight of a
+  h.wb = render_edge(x1, y1, x0, y0, px, py);      // edge c -> a, weight of b
+  h.wc = render_edge(x0, y0, x2, y2, px, py);      // edge a -> b, weight of c
+  h.area = h.wa + h.wb + h.wc;
+  const long long ea = h.wa - (render_owns_edge(x2, y2, x1, y1) ? 0 : 1);
+  const long long eb = h.wb - (render_owns_edge(x1, y1, x0, y0) ? 0 : 1);
+  const long long ec = h.wc - (render_owns_edge(x0, y0, x2, y2) ? 0 : 1);
+  return (ea | eb | ec) >= 0;
+}
+
+__global__ __launch_bounds__(256) void render_tile_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                          const float* __restrict__ vnorm, const int* __restrict__ fcoord,
+                                                          const int* __restrict__ fbox, const uint8_t* __restrict__ bg, float cr,
+                                                          float cg, float cb, int V, int F, int H, int W, int wide,
+                                                          uint8_t* __restrict__ out, int* __restrict__ face_id,
+                                                          float* __restrict__ depth) {
+  __shared__ int s_xy[2][6][RND_CHUNK];
+  __shared__ int s_box[2][2][RND_CHUNK];
+  __shared__ float s_z[2][3][RND_CHUNK];
+  __shared__ int s_f[2][RND_CHUNK];
+  __shared__ unsigned s_cnt[3];
+  __shared__ __attribute__((aligned(16))) uint8_t s_px[RND_TILE][RND_TILE * 3];
+  const int t = threadIdx.x, n = blockIdx.z;
+  const int tx0 = blockIdx.x * RND_TILE, ty0 = blockIdx.y * RND_TILE;
+  const int tx1 = rnd_min(tx0 + RND_TILE, W) - 1, ty1 = rnd_min(ty0 + RND_TILE, H) - 1;
+  const int lx = t & (RND_TILE - 1), ly = t >> 4;
+  const int i = tx0 + lx, j = ty0 + ly;
+  const bool live = i < W && j < H;
+  const int px = 256 * i + 128, py = 256 * j + 128;
+  const float* P = verts + (size_t)n * V * 3;
+  const int* C = fcoord + (size_t)n * F * 6;
+  const int* B = fbox + (size_t)n * F * 2;
+  const size_t img = (size_t)n * H * W;
+  // the frame under the mesh: 16-byte rows when the layout allows it (`wide`: W a multiple of 16 and 16-byte aligned bases)
+  if (wide) {
+    if (t < 3 * RND_TILE) {
+      const int r = t / 3, q = t - 3 * r;
+      rnd_u32x4 v = {0u, 0u, 0u, 0u};
+      if (bg && ty0 + r < H) v = *reinterpret_cast<const rnd_u32x4*>(bg + (img + (size_t)(ty0 + r) * W + tx0) * 3 + 16 * q);
+      *reinterpret_cast<rnd_u32x4*>(&s_px[r][16 * q]) = v;
+    }
+  } else {
+    const uint8_t* s = bg && live ? bg + (img + (size_t)j * W + i) * 3 : nullptr;
+    s_px[ly][3 * lx] = s ? s[0] : 0;
+    s_px[ly][3 * lx + 1] = s ? s[1] : 0;
+    s_px[ly][3 * lx + 2] = s ? s[2] : 0;
+  }
+  if (t < 3) s_cnt[t] = 0;
+  __syncthreads();
+
+  float best = __uint_as_float(0x7f800000u);      // +inf
+  int best_f = -1;
+  const int nchunks = (F + RND_CHUNK - 1) / RND_CHUNK;
+  for (int c = 0; c < nchunks; ++c) {
+    const int buf = c & 1, cn = c % 3;
+    // counter of the next chunk: last read two chunks ago, before the barrier every thread has passed since
+    if (t == 0) s_cnt[(c + 1) % 3] = 0;
+    const int f = c * RND_CHUNK + t;
+    if (f < F) {
+      const int bx = B[2 * f], by = B[2 * f + 1];
+      if ((bx & 0xffff) <= tx1 && (bx >> 16) >= tx0 && (by & 0xffff) <= ty1 && (by >> 16) >= ty0) {
+        const unsigned s = atomicAdd(&s_cnt[cn], 1u);
+        const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];      // in range: set-up gave a box
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s_xy[buf][k][s] = C[6 * (size_t)f + k];
+        s_box[buf][0][s] = bx;
+        s_box[buf][1][s] = by;
+        s_z[buf][0][s] = P[3 * i0 + 2];
+        s_z[buf][1][s] = P[3 * i1 + 2];
+        s_z[buf][2][s] = P[3 * i2 + 2];
+        s_f[buf][s] = f;
+      }
+    }
+    __syncthreads();
+    const int m = (int)s_cnt[cn];
+    if (live) {
+      for (int e = 0; e < m; ++e) {
+        const int bx = s_box[buf][0][e], by = s_box[buf][1][e];
+        if (i < (bx & 0xffff) || i > (bx >> 16) || j < (by & 0xffff) || j > (by >> 16)) continue;
+        RenderHit h;
+        if (!render_cover(s_xy[buf][0][e], s_xy[buf][1][e], s_xy[buf][2][e], s_xy[buf][3][e], s_xy[buf][4][e], s_xy[buf][5][e], px,
+                          py, h))
+          continue;
+        // weights of v0, v1, v2 = wa, wc, wb
+        const float d = ((float)h.wa * s_z[buf][0][e] + (float)h.wc * s_z[buf][1][e] + (float)h.wb * s_z[buf][2][e]) / (float)h.area;
+        const int f2 = s_f[buf][e];
+        if (d < best || (d == best && f2 < best_f) || best_f < 0) {
+          best = d;
+          best_f = f2;
+        }
+      }
+    }
+    // the entries of this chunk are overwritten two chunks on, behind the next barrier
+  }
+
+  if (live && best_f >= 0) {
+    const int i0 = faces[3 * best_f], i1 = faces[3 * best_f + 1], i2 = faces[3 * best_f + 2];
+    const int* c = C + 6 * (size_t)best_f;
+    RenderHit h;
+    render_cover(c[0], c[1], c[2], c[3], c[4], c[5], px, py, h);
+    const float ar = (float)h.area;
+    const float b0 = (float)h.wa / ar, b1 = (float)h.wc / ar, b2 = (float)h.wb / ar;
+    const float* N = vnorm + (size_t)n * V * 3;
+    float nx = b0 * N[3 * i0] + b1 * N[3 * i1] + b2 * N[3 * i2];
+    float ny = b0 * N[3 * i0 + 1] + b1 * N[3 * i1 + 1] + b2 * N[3 * i2 + 1];
+    float nz = b0 * N[3 * i0 + 2] + b1 * N[3 * i1 + 2] + b2 * N[3 * i2 + 2];
+    const float nl = sqrtf(nx * nx + ny * ny + nz * nz);
+    const float ni = nl > 0.f ? 1.f / nl : 0.f;
+    // the turned space: (x, -y, -z) for positions and normals alike
+    nx = nx * ni;
+    ny = -(ny * ni);
+    nz = -(nz * ni);
+    const float qx = b0 * P[3 * i0] + b1 * P[3 * i1] + b2 * P[3 * i2];
+    const float qy = -(b0 * P[3 * i0 + 1] + b1 * P[3 * i1 + 1] + b2 * P[3 * i2 + 1]);
+    const float qz = -(b0 * P[3 * i0 + 2] + b1 * P[3 * i1 + 2] + b2 * P[3 * i2 + 2]);
+    const float L[3][3] = {{0.f, -1.f, 1.f}, {0.f, 1.f, 1.f}, {1.f, 1.f, 2.f}};
+    float sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float dx = L[k][0] - qx, dy = L[k][1] - qy, dz = L[k][2] - qz;
+      const float dl = sqrtf(dx * dx + dy * dy + dz * dz);
+      const float dot = dl > 0.f ? (nx * dx + ny * dy + nz * dz) / dl : 0.f;
+      sum += fmaxf(dot, 0.f);
+    }
+    const float I = fminf(0.3f + 0.35f * sum, 1.f);
+    s_px[ly][3 * lx] = (uint8_t)fminf(fmaxf(rintf(255.f * I * cr), 0.f), 255.f);
+    s_px[ly][3 * lx + 1] = (uint8_t)fminf(fmaxf(rintf(255.f * I * cg), 0.f), 255.f);
+    s_px[ly][3 * lx + 2] = (uint8_t)fminf(fmaxf(rintf(255.f * I * cb), 0.f), 255.f);
+  }
+  if (live) {
+    if (face_id) face_id[img + (size_t)j * W + i] = best_f;
+    if (depth) depth[img + (size_t)j * W + i] = best_f >= 0 ? best : __uint_as_float(0x7f800000u);
+  }
+  __syncthreads();
+  if (wide) {
+    if (t < 3 * RND_TILE) {
+      const int r = t / 3, q = t - 3 * r;
+      if (ty0 + r < H)
+        *reinterpret_cast<rnd_u32x4*>(out + (img + (size_t)(ty0 + r) * W + tx0) * 3 + 16 * q) =
+            *reinterpret_cast<const rnd_u32x4*>(&s_px[r][16 * q]);
+    }
+  } else if (live) {
+    uint8_t* o = out + (img + (size_t)j * W + i) * 3;
+    o[0] = s_px[ly][3 * lx];
+    o[1] = s_px[ly][3 * lx + 1];
+    o[2] = s_px[ly][3 * lx + 2];
+  }
+}
+
+// scratch: vertex normals [N][V][3] fp32 (first, so a caller can read them back), snapped corners [N][F][6] int32, boxes [N][F][2] int32
+extern "C" size_t dyb_render_workspace_bytes(int N, int V, int F) {
+  if (N <= 0 || V <= 0 || F <= 0) return 0;
+  return rnd_align((size_t)N * V * 3 * sizeof(float)) + rnd_align((size_t)N * F * 6 * sizeof(int)) +
+         rnd_align((size_t)N * F * 2 * sizeof(int));
+}
+
+extern "C" int dyb_render_meshes(const float* verts, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
+                                 const uint8_t* background, float col_r, float col_g, float col_b, uint8_t* out, int* face_id,
+                                 float* depth, int N, int V, int F, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
+  DYB_REQUIRE(verts && faces && adj_ptr && adj_idx && cam && out && ws, DYB_ERR_ARG);
+  DYB_REQUIRE(N > 0 && V > 0 && F > 0 && H > 0 && W > 0, DYB_ERR_ARG);
+  DYB_REQUIRE(N <= RND_MAX_N && H <= RND_MAX_DIM && W <= RND_MAX_DIM, DYB_ERR_UNSUPPORTED);
+  DYB_REQUIRE(F <= (1 << 28) && V <= (1 << 28), DYB_ERR_UNSUPPORTED);                  // 3 F and 3 V stay inside int
+  DYB_REQUIRE(ws_bytes >= dyb_render_workspace_bytes(N, V, F), DYB_ERR_WORKSPACE);
+  char* w = reinterpret_cast<char*>(ws);
+  float* vnorm = reinterpret_cast<float*>(w);
+  w += rnd_align((size_t)N * V * 3 * sizeof(float));
+  int* fcoord = reinterpret_cast<int*>(w);
+  w += rnd_align((size_t)N * F * 6 * sizeof(int));
+  int* fbox = reinterpret_cast<int*>(w);
+  hipLaunchKernelGGL(render_vnormal_kernel, dim3(dyb_cdiv(V, 256), 1, N), dim3(256), 0, st, verts, faces, adj_ptr, adj_idx, V, F, vnorm);
+  DYB_CHECK_LAUNCH();
+  hipLaunchKernelGGL(render_face_setup_kernel, dim3(dyb_cdiv(F, 256), 1, N), dim3(256), 0, st, verts, faces, cam, V, F, H, W, fcoord, fbox);
+  DYB_CHECK_LAUNCH();
+  const int wide = W % 16 == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)background & 15) == 0;
+  hipLaunchKernelGGL(render_tile_kernel, dim3(dyb_cdiv(W, RND_TILE), dyb_cdiv(H, RND_TILE), N), dim3(256), 0, st, verts, faces,
+                     (const float*)vnorm, (const int*)fcoord, (const int*)fbox, background, col_r, col_g, col_b, V, F, H, W, wide, out,
+                     face_id, depth);
+  DYB_CHECK_LAUNCH();
+  return DYB_OK;
+}

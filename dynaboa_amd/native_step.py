@@ -31,6 +31,8 @@ def coverage(o, have_bundle: bool = True):
         return "", "frame losses switched off"
     if g("dump_predictions"):
         return "", "prediction dumps"
+    if g("save_res"):
+        return "", "rendered results"
     if not g("share_forwards", 1) or not g("fused_level", 1):
         return "", "unshared / unfused schedule requested"
     temporal = (g("use_temporal_losses_lower") or g("use_temporal_losses_upper")) and (g("use_meanteacher") or g("use_motion"))

@@ -1,0 +1,149 @@
+"""Mesh overlay: the reference's ``render_demo.py`` surface - ``Renderer(resolution, orig_img, wireframe)`` with
+``.render(img, verts, cam, color=...)`` and ``convert_crop_cam_to_orig_img`` - on the HIP rasteriser of csrc/render.hip.
+
+The reference draws one frame at a time with pyrender on OpenGL through the host; here the vertices, the camera and the frame stay
+on the device and a batch of meshes (one per sequence of a step, up to 64) is drawn by one call.  Geometry, visibility, the ambient
+term and the three light positions are the reference's; the material model is plain smooth diffuse shading, NOT pyrender's
+metallic-roughness one (unpinned: pyrender is absent from the build image).  Conventions: csrc/render.hip."""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._abi import check
+from .hmr import stream_of
+
+MAX_MESHES = 64
+MAX_DIM = 4096
+DEFAULT_COLOR = (1.0, 1.0, 0.9)          # render_demo.py:86
+
+
+def vertex_face_csr(faces: np.ndarray, num_verts: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(ptr [V+1], idx [3F]) int32: the faces incident to each vertex, ascending per vertex (a face naming a vertex twice is
+    listed twice under it)."""
+    flat = np.asarray(faces, np.int64).reshape(-1)
+    order = np.argsort(flat, kind="stable")
+    ptr = np.zeros(num_verts + 1, np.int64)
+    np.cumsum(np.bincount(flat, minlength=num_verts), out=ptr[1:])
+    return ptr.astype(np.int32), (order // 3).astype(np.int32)
+
+
+def convert_crop_cam_to_orig_img(cam, bbox, img_width, img_height):
+    """Weak-perspective camera (s, tx, ty) of the square crop -> (sx, sy, tx, ty) in the original frame, for boxes (cx, cy, h)
+    in frame pixels (what reference render_demo.py:136-153 computes).  cam (B, 3), bbox (B, 3); numpy or torch -> (B, 4).
+
+    The crop shows the h x h box centred at (cx, cy).  In normalised coordinates (-1 ... 1 across an image) a crop position q
+    lies at  h / (W, H) * q + (2 (cx, cy) / (W, H) - 1)  of the frame, and the crop camera puts the model point X at
+    q = s (X + t).  Written again as scale * (X + shift):  scale = s h / (W, H),  shift = t + (2 (cx, cy) / (W, H) - 1) / scale."""
+    if torch.is_tensor(cam):
+        frame, cat = cam.new_tensor([float(img_width), float(img_height)]), torch.cat
+        bbox = bbox.to(cam.device, cam.dtype)
+    else:
+        frame, cat = np.array([float(img_width), float(img_height)]), np.concatenate
+    scale = cam[:, :1] * bbox[:, 2:3] / frame
+    shift = cam[:, 1:3] + (2.0 * bbox[:, :2] / frame - 1.0) / scale
+    return cat([scale, shift], 1)
+
+
+class Renderer:
+    """``resolution`` is (width, height) as in the reference.  ``faces``: the (F, 3) table an ``SMPL`` carries (``smpl.faces``);
+    the int32 copy and the vertex -> face adjacency are built once here.  ``device``: where numpy inputs are drawn."""
+
+    def __init__(self, resolution=(224, 224), orig_img=False, wireframe=False, faces=None, device=None):
+        if wireframe:
+            raise NotImplementedError("wireframe rendering is not implemented (reference RenderFlags.ALL_WIREFRAME)")
+        if faces is None:
+            raise ValueError("Renderer needs the mesh's face table: faces=smpl.faces")
+        self.resolution = (int(resolution[0]), int(resolution[1]))
+        self.orig_img = orig_img
+        self.wireframe = wireframe
+        f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
+        if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] == 0:
+            raise ValueError("faces must be (F, 3)")
+        if f.min() < 0:
+            raise ValueError("negative vertex index in faces")
+        self.faces = np.ascontiguousarray(f, dtype=np.int32)
+        self.min_verts = int(f.max()) + 1
+        self.device = torch.device(device) if device is not None else None
+        self._tables: Dict[tuple, tuple] = {}
+        self._ws: Dict[tuple, torch.Tensor] = {}
+
+    def _adjacency(self, V: int, dev: torch.device):
+        key = (V, str(dev))
+        hit = self._tables.get(key)
+        if hit is None:
+            ptr, idx = vertex_face_csr(self.faces, V)
+            hit = self._tables[key] = tuple(torch.from_numpy(a).to(dev) for a in (self.faces, ptr, idx))
+        return hit
+
+    def _device_of(self, *xs) -> torch.device:
+        for x in xs:
+            if torch.is_tensor(x):
+                return x.device
+        if self.device is not None:
+            return self.device
+        return torch.device("cuda" if torch.cuda.is_available() else "cpu")
+
+    def rasterize(self, verts, cam, img=None, color: Sequence[float] = DEFAULT_COLOR, return_normals=False):
+        """-> (image uint8 (N, H, W, 3), face_id int32 (N, H, W), -1 where nothing is drawn, depth fp32 (N, H, W), +inf there);
+        without the leading N for a single mesh.  Torch tensors on the inputs' device, or numpy arrays for numpy inputs.
+        ``return_normals`` (a debug output) appends the call's vertex normals (N, V, 3), copied out of the workspace."""
+        as_numpy = not torch.is_tensor(verts)
+        dev = self._device_of(verts, cam, img)
+        v = torch.as_tensor(verts, dtype=torch.float32, device=dev) if as_numpy else verts.detach().to(dev, torch.float32)
+        c = torch.as_tensor(np.asarray(cam) if not torch.is_tensor(cam) else cam.detach()).to(dev, torch.float32)
+        single = v.dim() == 2
+        if single:
+            v, c = v[None], c.reshape(1, -1)
+        if v.dim() != 3 or v.shape[2] != 3 or c.shape != (v.shape[0], 4):
+            raise ValueError("verts must be (N, V, 3) or (V, 3) and cam (N, 4) or (4,) = (sx, sy, tx, ty)")
+        v, c = v.contiguous(), c.contiguous()
+        N, V = int(v.shape[0]), int(v.shape[1])
+        W, H = self.resolution
+        if V < self.min_verts:
+            raise ValueError(f"faces index vertex {self.min_verts - 1} but the mesh has {V} vertices")
+        bg = None
+        if img is not None:
+            bg = torch.as_tensor(img).to(dev)
+            if bg.dtype != torch.uint8:
+                raise ValueError("the frame under the mesh must be uint8 RGB")
+            if single and bg.dim() == 3:
+                bg = bg[None]
+            if tuple(bg.shape) != (N, H, W, 3):
+                raise ValueError(f"frame shape {tuple(bg.shape)} does not match (N, H, W, 3) = {(N, H, W, 3)}")
+            bg = bg.contiguous()
+        lib = _lib.load()
+        faces, ptr, idx = self._adjacency(V, dev)
+        F = int(faces.shape[0])
+        nbytes = int(lib.dyb_render_workspace_bytes(N, V, F))
+        sid = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+        ws = self._ws.get((str(dev), sid))
+        if ws is None or ws.numel() < nbytes:
+            ws = self._ws[(str(dev), sid)] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=dev)
+        fid = torch.empty(N, H, W, dtype=torch.int32, device=dev)
+        depth = torch.empty(N, H, W, dtype=torch.float32, device=dev)
+        col = [float(x) for x in color]
+        check(lib.dyb_render_meshes(v.data_ptr(), faces.data_ptr(), ptr.data_ptr(), idx.data_ptr(), c.data_ptr(),
+                                    bg.data_ptr() if bg is not None else None, col[0], col[1], col[2], out.data_ptr(), fid.data_ptr(),
+                                    depth.data_ptr(), N, V, F, H, W, ws.data_ptr(), ws.numel(), stream_of(v)), "dyb_render_meshes")
+        res = (out, fid, depth)
+        if return_normals:
+            res += (ws[:N * V * 12].view(torch.float32).view(N, V, 3).clone(),)
+        if single:
+            res = tuple(r[0] for r in res)
+        if as_numpy:
+            res = tuple(r.cpu().numpy() for r in res)
+        return res
+
+    def render(self, img, verts, cam, angle=None, axis=None, mesh_filename=None, color: Sequence[float] = DEFAULT_COLOR):
+        """The mesh (or batch of meshes) drawn over ``img`` (uint8 RGB, (H, W, 3) or (N, H, W, 3); None = black), as uint8 of the
+        kind ``verts`` came in.  ``cam`` = (sx, sy, tx, ty)."""
+        if angle or axis:
+            raise NotImplementedError("rotating the mesh before rendering (the reference's side views) is not implemented")
+        if mesh_filename is not None:
+            raise NotImplementedError(".obj export is not implemented")
+        return self.rasterize(verts, cam, img, color)[0]

@@ -448,6 +448,24 @@ int dyb_crop_resize_normalize(const uint8_t* img, int H, int W, int ul_x, int ul
                               float mean0, float mean1, float mean2, float std0, float std1, float std2, void* ws,
                               size_t ws_bytes, dyb_stream_t stream);
 
+/* ---- mesh overlay: N meshes rasterised over their frames in one call ---------------------------------------------------
+ * Stands where the reference renders one frame at a time through pyrender (render_demo.py:58-134, called from
+ * base_adaptor.py:429-443).  verts [N][V][3] fp32; faces [F][3] int32, shared by the N meshes; (adj_ptr [V+1], adj_idx [3F]):
+ * vertex -> incident faces as CSR, ascending face index per vertex (the vertex normals are gathered in that order);
+ * cam [N][4] = (sx, sy, tx, ty); background [N][H][W][3] uint8 RGB or NULL (black); out [N][H][W][3] uint8;
+ * face_id [N][H][W] int32 (-1 = not covered) and depth [N][H][W] fp32 (+inf = not covered) are optional (NULL).
+ * Image position u = W/2 (1 + sx (X + tx)), v = H/2 (1 + sy (Y + ty)), pixel centres at (i + 0.5, j + 0.5), depth = Z (smaller
+ * is nearer, no clipping planes).  Coverage is exact: positions snapped to 1/256 pixel, int64 edge functions, top-left rule;
+ * faces whose normal (v1 - v0) x (v2 - v0) has Z >= 0 after snapping are culled, and so is a face with a corner beyond 2^22
+ * pixels.  Nearest face wins, ties to the lower index; the result does not depend on scheduling (two calls give equal bytes).
+ * Smooth shading with the reference's ambient 0.3 and three light positions; pyrender's own material model is not
+ * reproduced (csrc/render.hip).  N <= 64, H and W <= 4096 (DYB_ERR_UNSUPPORTED beyond).  ws: dyb_render_workspace_bytes(N, V, F);
+ * after the call its first N * V * 3 floats hold the vertex normals.  Nothing is written when an error code is returned. */
+size_t dyb_render_workspace_bytes(int N, int V, int F);
+int dyb_render_meshes(const float* verts, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
+                      const uint8_t* background, float col_r, float col_g, float col_b, uint8_t* out, int* face_id,
+                      float* depth, int N, int V, int F, int H, int W, void* ws, size_t ws_bytes, dyb_stream_t stream);
+
 /* ---- native frame stepper: Adaptor.adaptation (reference dynaboa_benchmark.py:126-193) as ONE call per frame --------
  * The first-order bilevel schedule with the frame-loss set - clone, inner_step x [lower-level loss
  * (base_adaptor.py:222-268) -> learner.adapt -> inference], upper-level loss (:270-317) through the fast weights,
