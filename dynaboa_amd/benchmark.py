@@ -333,26 +333,8 @@ class Adaptor(BaseAdaptor):
                     log[f"{tag}/{k}"] = r[10 + j]
             log[f"{tag}/total"] = r[15]
         self.kp2dlosses_upper[self.global_step] = lrow(K)[0]
-        out = (None, None, None)
         nfinal = 1 + (min(extra, o.optim_steps) if o.dynamic_boa else 0)
-        tags = ([('lower', i) for i in range(K)] if getattr(o, "eval_lower", 1) else []) + [('final', k) for k in range(nfinal)]
-        stats_m, stats_p = [], []
-        for tag in tags:
-            v = ns.record_views(slot, rr)
-            slot += 1
-            if o.deferred_metrics:
-                self._pending.append(dict(step=self.global_step, tag=tag, **v))
-                res = (v["mpjpe"], None, v["pve"])
-            else:
-                pa = pa_mpjpe_device(v["pred"], v["gt"]).cpu().numpy()
-                res = (v["mpjpe"].cpu().numpy() * 1000, pa * 1000, float(v["pve"]) * 1000)
-            if tag[0] == 'lower':
-                self.mpjpe_all_lower[tag[1]].append(res[0]); self.pampjpe_all_lower[tag[1]].append(res[1])
-            else:
-                out = res
-                stats_m.append(res[0]); stats_p.append(res[1])
-        if self.global_step < len(self.mpjpe_statistics):
-            self.mpjpe_statistics[self.global_step], self.pampjpe_statistics[self.global_step] = stats_m, stats_p
+        out = self._native_records(slot, nfinal)
         if o.dynamic_boa:
             cos, means = ns.gate_views(f, rr)                                 # views cut once per frame for all sequences (native_step.py)
             self.feat_sims[self.global_step] = [{i: {"cos": c} for i, c in enumerate(cos[k])} for k in range(nfinal)]
@@ -374,10 +356,17 @@ class Adaptor(BaseAdaptor):
             log[f"{tag}/s2dloss"], log[f"{tag}/shape_prior"], log[f"{tag}/pose_prior"] = l4[0], l4[1], l4[2]
             log[f"{tag}/unlabelloss"] = log[f"{tag}/total"] = l4[3]
         self.kp2dlosses_upper[self.global_step] = log["ul/s2dloss"]
-        out = (None, None, None)
-        tags = ([('lower', i) for i in range(K)] if getattr(o, "eval_lower", 1) else []) + [('final', 0)]
         if not o.deferred_metrics:
             ns.join()
+        return self._native_records(slot, 1)
+
+    def _native_records(self, slot, nfinal):
+        """The frame's metric records from the stepper's device buffers, in schedule order from `slot`: one per inner step (eval_lower),
+        then `nfinal` final inferences (> 1: the dynamic loop's) -> the last final one's (mpjpe, pampjpe, pve)."""
+        o, ns, r = self.options, self._native, getattr(self, "_native_replica", 0)
+        out = (None, None, None)
+        tags = ([('lower', i) for i in range(o.inner_step)] if getattr(o, "eval_lower", 1) else []) + [('final', k) for k in range(nfinal)]
+        stats_m, stats_p = [], []
         for tag in tags:
             v = ns.record_views(slot, r)
             slot += 1
@@ -391,9 +380,9 @@ class Adaptor(BaseAdaptor):
                 self.mpjpe_all_lower[tag[1]].append(res[0]); self.pampjpe_all_lower[tag[1]].append(res[1])
             else:
                 out = res
+                stats_m.append(res[0]); stats_p.append(res[1])
         if self.global_step < len(self.mpjpe_statistics):
-            self.mpjpe_statistics[self.global_step] = [out[0]]
-            self.pampjpe_statistics[self.global_step] = [out[1]]
+            self.mpjpe_statistics[self.global_step], self.pampjpe_statistics[self.global_step] = stats_m, stats_p
         return out
 
     # ------------------------------------------------------------------ the per-frame bilevel step

@@ -20,15 +20,12 @@
 #include <string.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <condition_variable>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "dyb_common.h"
+#include "dyb_stepper_options.h"
 
 extern "C" {
 size_t dyb_hmr_param_floats(const void*);
@@ -231,9 +228,6 @@ struct Pass {
   float* pred17;
 };
 
-struct SideIssuer;
-struct Stepper;
-static void side_shutdown(Stepper& S);
 struct Stepper {
   void* plan = nullptr;
   int B = 1, H = 224, W = 224;
@@ -288,8 +282,7 @@ struct Stepper {
   int record_capacity = 0, loss_capacity = 0;
   // workspace
   char* wsp = nullptr;
-  size_t wsp_bytes = 0;
-  bool bound = false, fresh = true;
+  bool bound = false;
   Pass main{}, fin{};
   float *theta_fast = nullptr, *grads = nullptr;
   // "fuse_fast" (round 6; frame-loss path): a lower level's unsplit throughput-form weight gradients write theta_next = theta_cur - fastlr * g
@@ -325,7 +318,6 @@ struct Stepper {
   hipEvent_t par_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // fork | hist fwd | hist head grads | hist bwd | label term | exemplar bwd | error-path tails of the two pass streams
   bool out_in_main = false;        // where the latest final inference lives (dyb_stepper_output): fin, or main after an odd number of shared steps
   int share_dyn_fwd = 1;           // dynamic loop: an extra step's upper level reuses the previous step's final inference as its forward
-  int upd_blocks = 0;              // > 0: workgroup cap (all replicas together) of the ranged passes on the auxiliary stream (measured: no effect, 512 .. uncapped)
   hipEvent_t e_upd = nullptr;
   DybFwdGates gates{};
   bool gates_pending = false;
@@ -339,15 +331,18 @@ struct Stepper {
   bool defer_pending = false;      // a deferred set has been issued that no consumer has been ordered behind yet
   int n_deferred = 0;              // launches issued behind a backward's join so far (get_f "deferred_launches": what the tests count)
   int upd_late = 1;                // the last range (layer4 + regressor, 68 % of the parameters) is issued when the forward reaches layer3
-  struct LateUpd {                 // what gates.late needs to issue it
-    Stepper* S = nullptr;
+  // one weight update: the fast-weight step out = p - fastlr * g (adam = false), or Adam in place on theta [+ the teacher's EMA]
+  struct Upd {
     bool adam = false, ema = false;
-    const float *g2 = nullptr, *g3 = nullptr;
+    const float *g2 = nullptr, *g3 = nullptr;      // the level's further gradient arenas, summed by the pass
     const float* p = nullptr;
     float* out = nullptr;
+    float ss[DYB_MAX_REPLICAS] = {}, bc[DYB_MAX_REPLICAS] = {};     // Adam's bias corrections by physical replica
+  };
+  struct LateUpd {                 // what gates.late needs to issue it
+    Upd u;
     hipStream_t aux = nullptr;
     DybRep scope{};
-    float ss[DYB_MAX_REPLICAS], bc[DYB_MAX_REPLICAS];
   } late;
   size_t grp_bounds[2] = {0, 0};
   bool side_pending = false;
@@ -366,13 +361,6 @@ struct Stepper {
     const float *pose = nullptr, *betas = nullptr;
   } gtjob;
   hipStream_t tail_stream = nullptr;
-  // "side_thread" (one sequence with a side stream): the side stream's launches - the previous frame's final forward, this frame's
-  // ground-truth meshes, ~130 launches - are issued by a helper thread while the calling thread goes on with the frame's chain.  At one
-  // sequence the frame is bound by the host's launch rate (~1 400 launches at ~8 us; profiles/r04_frame_timeline_S1.txt: the main queue
-  // sat idle for 1.1 ms per frame while the calling thread issued them).  The calling thread waits for the helper before it first
-  // touches anything the helper writes (e_gt, side_pending, the tail slot).
-  int side_thread = 0;
-  SideIssuer* issuer = nullptr;
   std::string err;
   // host-side issue time by section (always on: two clock reads per section), read back through dyb_stepper_get_f
   double h_fwd = 0, h_bwd = 0, h_head = 0, h_update = 0, h_tail = 0, h_total = 0;
@@ -386,6 +374,7 @@ struct HostTimer {
 };
 
 static size_t a64(size_t v) { return (v + 63) & ~(size_t)63; }
+static const char* opt_env(const char* name) { return name ? getenv(name) : nullptr; }
 
 // carve (or, with base == nullptr, size) the workspace
 static size_t carve(Stepper& S, char* base) {
@@ -482,16 +471,11 @@ extern "C" int dyb_stepper_create(void* plan, int B, int H, int W, void** out) {
   S->lbs_wsb = dyb_lbs_bwd_workspace_bytes(B);
   S->ev = dyb_hmr_events_create(plan);
   dyb_hmr_param_groups(plan, S->grp_bounds);
-  if (const char* e = getenv("DYB_UPD_OVERLAP")) S->upd_overlap = atoi(e);       // (A/B runs; set_i "upd_overlap" afterwards wins)
-  if (const char* e = getenv("DYB_UPD_BLOCKS")) S->upd_blocks = atoi(e);
-  if (const char* e = getenv("DYB_SHARE_DYN_FWD")) S->share_dyn_fwd = atoi(e);
-  if (const char* e = getenv("DYB_UPD_LATE")) S->upd_late = atoi(e);
-  if (const char* e = getenv("DYB_WGRAD_DEFER")) S->wgrad_defer = atoi(e);
-  if (const char* e = getenv("DYB_FUSE_FAST")) S->fuse_fast = atoi(e);
-  if (const char* e = getenv("DYB_FUSE_ADAM")) S->fuse_adam = atoi(e);
-  if (const char* e = getenv("DYB_FUSE_EMA")) S->fuse_ema = atoi(e);
-  if (const char* e = getenv("DYB_PAR_PASSES")) S->par_passes = atoi(e);
-  if (const char* e = getenv("DYB_PAR_MAX_REPLICAS")) S->par_max_replicas = atoi(e);
+  // (A/B runs; a set_i of the same option afterwards wins)
+#define DYB_OPT_ENV_(member, name, env, type, locked, doc) \
+  if (const char* e = opt_env(env)) S->member = atoi(e);
+  DYB_STEPPER_OPTIONS_I(DYB_OPT_ENV_)
+#undef DYB_OPT_ENV_
   if (!S->ev || hipEventCreateWithFlags(&S->e_theta, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&S->e_side, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&S->e_gt, hipEventDisableTiming) != hipSuccess ||
@@ -510,7 +494,6 @@ extern "C" int dyb_stepper_create(void* plan, int B, int H, int W, void** out) {
 extern "C" void dyb_stepper_destroy(void* stepper) {
   Stepper* S = reinterpret_cast<Stepper*>(stepper);
   if (!S) return;
-  side_shutdown(*S);
   dyb_hmr_events_destroy(S->ev);
   if (S->e_theta) (void)hipEventDestroy(S->e_theta);
   if (S->e_side) (void)hipEventDestroy(S->e_side);
@@ -524,28 +507,20 @@ extern "C" void dyb_stepper_destroy(void* stepper) {
   delete S;
 }
 
-// ---- string-keyed setters (the whole configuration surface of the stepper; unknown key => DYB_ERR_ARG) -----------------
+// ---- string-keyed options: dyb_stepper_options.h is the list (unknown key => DYB_ERR_ARG); below it the keys with code of their own ------
 extern "C" int dyb_stepper_set_i(void* stepper, const char* key, long long v) {
   Stepper* S = reinterpret_cast<Stepper*>(stepper);
   DYB_REQUIRE(S && key, DYB_ERR_ARG);
   const std::string k(key);
-  if (k == "n_iter") S->n_iter = (int)v;
-  else if (k == "inner_step") S->inner_step = (int)v;
-  else if (k == "eval_lower") S->eval_lower = (int)v;
-  else if (k == "use_side") S->use_side = (int)v;
-  else if (k == "upd_overlap") S->upd_overlap = (int)v;
-  else if (k == "side_thread") S->side_thread = (int)v;
-  else if (k == "upd_blocks") S->upd_blocks = (int)v;
-  else if (k == "share_dyn_fwd") S->share_dyn_fwd = (int)v;
-  else if (k == "par_passes") S->par_passes = (int)v;
-  else if (k == "par_max_replicas") S->par_max_replicas = (int)v;
-  else if (k == "upd_late") S->upd_late = (int)v;
-  else if (k == "wgrad_defer") S->wgrad_defer = (int)v;
-  else if (k == "fuse_fast") { DYB_REQUIRE(!S->bound, DYB_ERR_ARG); S->fuse_fast = (int)v; }
-  else if (k == "fuse_adam") S->fuse_adam = (int)v;
-  else if (k == "fuse_ema") S->fuse_ema = (int)v;
-  else if (k == "metrics") S->metrics = (int)v;
-  else if (k == "adam_step") {
+#define DYB_OPT_SET_I_(member, name, env, type, locked, doc) \
+  if (k == name) {                                           \
+    DYB_REQUIRE(!(locked) || !S->bound, DYB_ERR_ARG);        \
+    S->member = (int)v;                                      \
+    return DYB_OK;                                           \
+  }
+  DYB_STEPPER_OPTIONS_I(DYB_OPT_SET_I_)
+#undef DYB_OPT_SET_I_
+  if (k == "adam_step") {
     S->adam_t = v;
     for (int r = 0; r < DYB_MAX_REPLICAS; ++r) S->adam_t_rep[r] = v;
   }
@@ -555,26 +530,13 @@ extern "C" int dyb_stepper_set_i(void* stepper, const char* key, long long v) {
     S->adam_t_rep[r] = v;
     if (v > S->adam_t) S->adam_t = v;
   }
-  else if (k == "full") S->full = (int)v;
-  else if (k == "temporal_lower") S->temporal_lower = (int)v;
-  else if (k == "temporal_upper") S->temporal_upper = (int)v;
-  else if (k == "use_teacher") S->use_teacher = (int)v;
-  else if (k == "teacher_train") S->teacher_train = (int)v;
   else if (k == "drop_seed") S->drop_seed = (unsigned long long)v;
   else if (k == "drop_offset") { S->drop_off = (unsigned long long)v; S->drop_used = 0; }
-  else if (k == "use_motion") S->use_motion = (int)v;
-  else if (k == "interval") S->interval = (int)v;
-  else if (k == "mix_lower") S->mix_lower = (int)v;
-  else if (k == "mix_upper") S->mix_upper = (int)v;
-  else if (k == "dynamic") S->dynamic = (int)v;
-  else if (k == "optim_steps") S->optim_steps = (int)v;
   else if (k == "replicas") {
     DYB_REQUIRE(v >= 1 && v <= DYB_MAX_REPLICAS && !S->bound, DYB_ERR_ARG);
     S->nrep = (int)v;
   }
   else if (k == "logs_bytes") S->logs_bytes = (size_t)v;
-  else if (k == "record_capacity") S->record_capacity = (int)v;
-  else if (k == "loss_capacity") S->loss_capacity = (int)v;
   else return DYB_ERR_ARG;
   return DYB_OK;
 }
@@ -582,68 +544,50 @@ extern "C" int dyb_stepper_set_f(void* stepper, const char* key, double v) {
   Stepper* S = reinterpret_cast<Stepper*>(stepper);
   DYB_REQUIRE(S && key, DYB_ERR_ARG);
   const std::string k(key);
-  if (k == "lr") S->lr = v;
-  else if (k == "beta1") S->beta1 = v;
-  else if (k == "beta2") S->beta2 = v;
-  else if (k == "eps") S->eps = v;
-  else if (k == "fastlr") S->fastlr = v;
-  else if (k == "s2dloss_weight") S->w2d = v;
-  else if (k == "shape_prior_weight") S->wshape = v;
-  else if (k == "pose_prior_weight") S->wpose = v;
-  else if (k == "teacherloss_weight") S->teacher_w = v;
-  else if (k == "drop_p") { DYB_REQUIRE(v >= 0.0 && v < 1.0, DYB_ERR_ARG); S->drop_p = v; }
-  else if (k == "motionloss_weight") S->motion_w = v;
-  else if (k == "labelloss_weight") S->label_w = v;
-  else if (k == "alpha") S->alpha = v;
-  else if (k == "cos_sim_threshold") S->cos_thr = v;
-  else return DYB_ERR_ARG;
-  return DYB_OK;
+  if (k == "drop_p") DYB_REQUIRE(v >= 0.0 && v < 1.0, DYB_ERR_ARG);
+#define DYB_OPT_SET_F_(member, name, env, type, locked, doc) \
+  if (k == name) {                                           \
+    S->member = v;                                           \
+    return DYB_OK;                                           \
+  }
+  DYB_STEPPER_OPTIONS_F(DYB_OPT_SET_F_)
+#undef DYB_OPT_SET_F_
+  return DYB_ERR_ARG;
 }
 // "smpl_<neutral|male|female>_<0..6>" = the seven float tables of dyb_lbs_fwd, "smpli_<...>_<0..2>" the three int tables
 extern "C" int dyb_stepper_set_p(void* stepper, const char* key, const void* p) {
   Stepper* S = reinterpret_cast<Stepper*>(stepper);
   DYB_REQUIRE(S && key, DYB_ERR_ARG);
   const std::string k(key);
-  static const char* const which[3] = {"neutral", "male", "female"};
-  if (k == "theta") S->theta = (float*)p;
-  else if (k == "adam_m") S->adam_m = (float*)p;
-  else if (k == "adam_v") S->adam_v = (float*)p;
-  else if (k == "init_state") S->init_state = (const float*)p;
-  else if (k == "gmm_means") S->gmm_means = (const float*)p;
-  else if (k == "gmm_precisions") S->gmm_prec = (const float*)p;
-  else if (k == "gmm_log_weights") S->gmm_logw = (const float*)p;
-  else if (k == "j_regressor_h36m") S->j_h36m = (const float*)p;
-  else if (k == "j14") S->j14 = (const int*)p;
-  else if (k == "logs_base") S->logs_base = (const char*)p;
-  else if (k == "records") S->records = (float*)p;
-  else if (k == "loss_log") S->loss_log = (float*)p;
-  else if (k == "teacher") S->teacher = (float*)p;
-  else if (k == "gate_host") S->gate_host = (volatile float*)p;
-  else if (k == "gate_log") S->gate_log = (float*)p;
-  else if (k == "feat5_out") S->feat5_out = (float*)p;
-  else if (k == "retrieve_fn") S->retrieve = (int (*)(void*, int, const void**))p;
-  else if (k == "retrieve_rep_fn") S->retrieve_rep = (int (*)(void*, int, int, const void**))p;
-  else if (k == "retrieve_user") S->retrieve_user = (void*)p;
-  else {
-    for (int g = 0; g < 3; ++g) {
-      const std::string pf = std::string("smpl_") + which[g] + "_", pi = std::string("smpli_") + which[g] + "_";
-      if (k.compare(0, pf.size(), pf) == 0 && k.size() == pf.size() + 1 && k.back() >= '0' && k.back() <= '6') {
-        S->smpl_f[g][k.back() - '0'] = (const float*)p;
-        return DYB_OK;
-      }
-      if (k.compare(0, pi.size(), pi) == 0 && k.size() == pi.size() + 1 && k.back() >= '0' && k.back() <= '2') {
-        S->smpl_i[g][k.back() - '0'] = (const int*)p;
-        return DYB_OK;
-      }
-    }
-    return DYB_ERR_ARG;
+#define DYB_OPT_SET_P_(member, name, env, type, locked, doc) \
+  if (k == name) {                                           \
+    S->member = (decltype(S->member))p;                      \
+    return DYB_OK;                                           \
   }
-  return DYB_OK;
+  DYB_STEPPER_OPTIONS_P(DYB_OPT_SET_P_)
+#undef DYB_OPT_SET_P_
+  static const char* const which[3] = {"neutral", "male", "female"};
+  for (int g = 0; g < 3; ++g) {
+    const std::string pf = std::string("smpl_") + which[g] + "_", pi = std::string("smpli_") + which[g] + "_";
+    if (k.compare(0, pf.size(), pf) == 0 && k.size() == pf.size() + 1 && k.back() >= '0' && k.back() <= '6') {
+      S->smpl_f[g][k.back() - '0'] = (const float*)p;
+      return DYB_OK;
+    }
+    if (k.compare(0, pi.size(), pi) == 0 && k.size() == pi.size() + 1 && k.back() >= '0' && k.back() <= '2') {
+      S->smpl_i[g][k.back() - '0'] = (const int*)p;
+      return DYB_OK;
+    }
+  }
+  return DYB_ERR_ARG;
 }
+// every int option of the list by its key, and the derived values below
 extern "C" long long dyb_stepper_get_i(const void* stepper, const char* key) {
   const Stepper* S = reinterpret_cast<const Stepper*>(stepper);
   if (!S || !key) return -1;
   const std::string k(key);
+#define DYB_OPT_GET_(member, name, env, type, locked, doc) \
+  if (k == name) return S->member;
+  DYB_STEPPER_OPTIONS_I(DYB_OPT_GET_)
   if (k == "adam_step") return S->adam_t;
   if (k.compare(0, 10, "adam_step_") == 0) {          // "adam_step_<replica>"
     const int r = atoi(k.c_str() + 10);
@@ -655,12 +599,14 @@ extern "C" long long dyb_stepper_get_i(const void* stepper, const char* key) {
   if (k == "slots_per_frame") return (S->eval_lower ? S->inner_step : 0) + 1 + (S->full && S->dynamic ? S->optim_steps : 0);
   return -1;
 }
-// host issue time (ms, accumulated over h_frames frame steps of the frame-loss path) by section:
-// "host_ms_forward", "host_ms_backward", "host_ms_head", "host_ms_update", "host_ms_tail", "host_ms_total", "host_frames"; "deferred_launches"
+// every double option of the list by its key; host issue time (ms, accumulated over "host_frames" frame steps) by section:
+// "host_ms_forward", "host_ms_backward", "host_ms_head", "host_ms_update", "host_ms_tail", "host_ms_total"; "deferred_launches"
 extern "C" double dyb_stepper_get_f(const void* stepper, const char* key) {
   const Stepper* S = reinterpret_cast<const Stepper*>(stepper);
   if (!S || !key) return -1.0;
   const std::string k(key);
+  DYB_STEPPER_OPTIONS_F(DYB_OPT_GET_)
+#undef DYB_OPT_GET_
   if (k == "host_ms_forward") return S->h_fwd;
   if (k == "host_ms_backward") return S->h_bwd;
   if (k == "host_ms_head") return S->h_head;
@@ -684,7 +630,6 @@ extern "C" int dyb_stepper_bind_workspace(void* stepper, void* ws, size_t bytes,
   S->blob = a64(carve(*S, nullptr) / 4) * 4;
   DYB_REQUIRE(bytes >= S->blob * (size_t)S->nrep, DYB_ERR_WORKSPACE);
   S->wsp = reinterpret_cast<char*>(ws);
-  S->wsp_bytes = bytes;
   carve(*S, S->wsp);                 // replica 0's pointers; replica r's = + r * blob (resolved inside the kernels)
   // the engine overwrites every tensor span of the gradient arena and only columns 144..156 of d_state: pads stay zero
   for (int r = 0; r < S->nrep; ++r) {
@@ -735,7 +680,7 @@ static int settle_update(Stepper& S, hipStream_t st);
 // HMR forward at `theta` -> rotmat / shape / cam in the pass's arena -> SMPL (neutral) vertices + 49 joints
 static int pass_forward(Stepper& S, Pass& P, const float* theta, const float* image, hipStream_t st, bool chain = true) {
   // (a ranged weight update may still be running on the auxiliary stream: this forward - the first reader of the new weights -
-  // waits for each range where it first reads it).  chain = false: the side stream's forward (possibly issued by the helper thread)
+  // waits for each range where it first reads it).  chain = false: a forward on the side stream or a pass stream
   // - never a consumer of a ranged update (replica groups have no side stream) and it leaves the chain's gate state alone
   const DybFwdGates* gates = (chain && S.gates_pending) ? &S.gates : nullptr;
   {
@@ -773,15 +718,6 @@ static int engine_backward(Stepper& S, Pass& P, const float* theta, float* grads
   if (defer) S.defer_pending = true;           // (also when the call fails half-way: settle_update then waits for what was issued)
   return dyb_hmr_backward_ev(S.plan, theta, P.acts, P.d_rot, P.d_state, S.n_iter, grads, P.ws, S.ws_bytes, st, aux, S.ev, defer, &S.n_deferred);
 }
-// gradient of the pass's loss total w.r.t. `theta` into `grads` (the same five C calls as fused_level._LevelFunction.backward)
-static int pass_backward(Stepper& S, Pass& P, const float* theta, float* grads, hipStream_t st, hipStream_t aux) {
-  RUN(dyb_scale_add(nullptr, P.djoints_l, nullptr, P.djoints, (size_t)S.B * NJ * 3, st));
-  RUN(dyb_lbs_bwd(S.smpl_f[0], S.smpl_i[0], P.acts + S.off_rot, P.saved, P.djoints, nullptr, P.drot_s, P.dbetas_s, 10, S.B, P.lbs_ws,
-                  S.lbs_wsb, st));
-  RUN(dyb_head_grad_combine(nullptr, P.drot_l, P.drot_s, nullptr, P.dshape_l, P.dbetas_s, nullptr, P.dcam_l, nullptr, P.d_rot,
-                            P.d_state, S.B, st));
-  return engine_backward(S, P, theta, grads, st, aux);
-}
 // ground-truth side of the metrics (depends on the batch only): male / female / neutral meshes from the axis-angle pose
 static int gt_meshes(Stepper& S, const float* gt_pose, const float* gt_betas, hipStream_t st) {
   RUN(dyb_rodrigues_fwd(gt_pose, S.gt_rot, S.B * 24, st));
@@ -801,11 +737,6 @@ static int record_metrics(Stepper& S, Pass& P, const long long* gender, int slot
   return DYB_OK;
 }
 
-// One adapted frame.  image [B][3][H][W], kp2d [B][49][3]; gt_pose [B][72] / gt_betas [B][10] / gender [B] (int64) feed the
-// metric records only (NULL with metrics = 0).  Records: inner_step (eval_lower) + 1 slots starting at record_slot, in
-// schedule order - after inner step 0, 1, ..., then the final one; losses: loss_slot*(inner_step+1) 4-vectors
-// (s2d, shape prior, pose prior, weighted total) per level.  side (may be NULL): stream for the final no-grad forward and
-// its metrics, overlapped with the next frame's first level; the call orders the weight hazards itself.
 // issue what the side stream owes: the previous frame's final forward + record, then this frame's ground-truth meshes
 static int issue_side_work(Stepper& S, hipStream_t side) {
   if (S.tail.on) {
@@ -823,84 +754,21 @@ static int issue_side_work(Stepper& S, hipStream_t side) {
   }
   return DYB_OK;
 }
-struct SideIssuer {
-  std::thread th;
-  std::mutex mu;
-  std::condition_variable cv;
-  bool has_job = false, quit = false;
-  std::atomic<int> busy{0};          // 1 from the post until every launch of the job has been issued
-  int rc = DYB_OK;
-  int device = 0;
-  Stepper* S = nullptr;
-  hipStream_t side = nullptr;
-  void main() {
-    (void)hipSetDevice(device);
-    for (;;) {
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return has_job || quit; });
-        if (quit) return;
-        has_job = false;
-      }
-      rc = issue_side_work(*S, side);
-      busy.store(0, std::memory_order_release);
-    }
-  }
-};
-// the helper is idle and what it wrote is visible; returns its last result
-static int side_wait(Stepper& S) {
-  SideIssuer* I = S.issuer;
-  if (!I) return DYB_OK;
-  while (I->busy.load(std::memory_order_acquire)) std::this_thread::yield();
-  const int rc = I->rc;
-  I->rc = DYB_OK;
-  return rc;
-}
-// issue_side_work, by the helper thread when there is one
-static int side_post(Stepper& S, hipStream_t side) {
-  if (!S.side_thread || dyb_rep_current().n != 1) return issue_side_work(S, side);
-  if (!S.issuer) {
-    S.issuer = new SideIssuer();
-    S.issuer->S = &S;
-    if (hipGetDevice(&S.issuer->device) != hipSuccess) S.issuer->device = 0;
-    S.issuer->th = std::thread([I = S.issuer] { I->main(); });
-  }
-  RUN(side_wait(S));
-  SideIssuer* I = S.issuer;
-  I->side = side;
-  I->busy.store(1, std::memory_order_release);
-  {
-    std::lock_guard<std::mutex> lk(I->mu);
-    I->has_job = true;
-  }
-  I->cv.notify_one();
-  return DYB_OK;
-}
-static void side_shutdown(Stepper& S) {
-  SideIssuer* I = S.issuer;
-  if (!I) return;
-  (void)side_wait(S);
-  {
-    std::lock_guard<std::mutex> lk(I->mu);
-    I->quit = true;
-  }
-  I->cv.notify_one();
-  if (I->th.joinable()) I->th.join();
-  delete I;
-  S.issuer = nullptr;
-}
-// out[lo, hi) = p - fastlr * (grads [+ g2 + g3]) minus the spans the level's weight gradients updated themselves (S.upd_spans, sorted)
-static int fastweight_range(Stepper& S, const float* p, float* out, const float* g2, const float* g3, size_t lo, size_t hi, hipStream_t s) {
-  bool any = false;
+// ---- weight updates ---------------------------------------------------------------------------------------------------
+static bool spans_touch(const Stepper& S, size_t lo, size_t hi) {
   for (const DybSpan& sp : S.upd_spans)
-    if (sp.off < hi && sp.off + sp.n > lo) { any = true; break; }
-  if (!any)
-    return dyb_fastweight_update3(p + lo, S.grads + lo, g2 ? g2 + lo : nullptr, g3 ? g3 + lo : nullptr, out + lo, (float)S.fastlr, hi - lo, s);
-  DYB_REQUIRE(!g2 && !g3 && lo % 4 == 0 && hi % 4 == 0, DYB_ERR_UNSUPPORTED);     // (the fused form exists for single-pass levels only)
+    if (sp.off < hi && sp.off + sp.n > lo) return true;
+  return false;
+}
+// [lo, hi) minus the spans the level's weight gradients updated themselves (S.upd_spans, sorted): the gaps between them as float4
+// segments, handed to `emit` in batches of up to DYB_FW_MAX_SEGS
+template <class Emit>
+static int walk_gaps(const Stepper& S, size_t lo, size_t hi, Emit emit) {
+  DYB_REQUIRE(lo % 4 == 0 && hi % 4 == 0, DYB_ERR_UNSUPPORTED);
   DybFwSegs t{};
   auto flush = [&]() -> int {
     if (t.n == 0) return DYB_OK;
-    const int rc = dyb_fastweight_update_segs(p, S.grads, out, (float)S.fastlr, t, s);
+    const int rc = emit(t);
     t.n = 0;
     return rc;
   };
@@ -922,79 +790,66 @@ static int fastweight_range(Stepper& S, const float* p, float* out, const float*
   RUN(add(at, hi));
   return flush();
 }
-// Adam over [lo, hi) minus the spans the outer level's weight gradients updated themselves (S.upd_spans, sorted)
+// out[lo, hi) = p - fastlr * (grads [+ g2 + g3]) minus the fused spans
+static int fastweight_range(Stepper& S, const float* p, float* out, const float* g2, const float* g3, size_t lo, size_t hi, hipStream_t s) {
+  if (!spans_touch(S, lo, hi))
+    return dyb_fastweight_update3(p + lo, S.grads + lo, g2 ? g2 + lo : nullptr, g3 ? g3 + lo : nullptr, out + lo, (float)S.fastlr, hi - lo, s);
+  DYB_REQUIRE(!g2 && !g3, DYB_ERR_UNSUPPORTED);     // (the fused form exists for single-pass levels only)
+  return walk_gaps(S, lo, hi, [&](const DybFwSegs& t) { return dyb_fastweight_update_segs(p, S.grads, out, (float)S.fastlr, t, s); });
+}
+// Adam over [lo, hi) minus the fused spans (ema: the teacher's EMA of the range in the same pass - "fuse_ema", default term set)
 static int adam_range(Stepper& S, const float* g2, const float* g3, const float* ss, const float* bc, size_t lo, size_t hi, hipStream_t s,
-                      bool ema = false) {
-  bool any = false;
-  for (const DybSpan& sp : S.upd_spans)
-    if (sp.off < hi && sp.off + sp.n > lo) { any = true; break; }
-  if (!any)      // (ema: the teacher's EMA of the range in the same pass - "fuse_ema", default term set)
+                      bool ema) {
+  if (!spans_touch(S, lo, hi))
     return dyb_adam_step_rep3_ema(S.theta + lo, S.grads + lo, g2 ? g2 + lo : nullptr, g3 ? g3 + lo : nullptr, S.adam_m + lo, S.adam_v + lo,
                                   (float)S.beta1, (float)S.beta2, ss, bc, (float)S.eps, hi - lo, ema ? S.teacher + lo : nullptr, (float)S.alpha, s);
-  DYB_REQUIRE(!ema, DYB_ERR_UNSUPPORTED);
-  DYB_REQUIRE(!g2 && !g3 && lo % 4 == 0 && hi % 4 == 0, DYB_ERR_UNSUPPORTED);
-  DybFwSegs t{};
-  auto flush = [&]() -> int {
-    if (t.n == 0) return DYB_OK;
-    const int rc = dyb_adam_step_segs(S.theta, S.grads, S.adam_m, S.adam_v, (float)S.beta1, (float)S.beta2, ss, bc, (float)S.eps, t, s);
-    t.n = 0;
-    return rc;
-  };
-  auto add = [&](size_t a, size_t b) -> int {
-    if (a >= b) return DYB_OK;
-    DYB_REQUIRE(a % 4 == 0 && b % 4 == 0 && (b - a) / 4 < 0xffffffffull && a / 4 < 0xffffffffull, DYB_ERR_UNSUPPORTED);
-    if (t.n == DYB_FW_MAX_SEGS) RUN(flush());
-    t.start4[t.n] = (unsigned)(a / 4); t.count4[t.n] = (unsigned)((b - a) / 4); ++t.n;
-    return DYB_OK;
-  };
-  size_t at = lo;
-  for (const DybSpan& sp : S.upd_spans) {
-    if (sp.off + sp.n <= at) continue;
-    if (sp.off >= hi) break;
-    DYB_REQUIRE(sp.off >= lo && sp.off + sp.n <= hi, DYB_ERR_UNSUPPORTED);
-    RUN(add(at, sp.off));
-    at = sp.off + sp.n;
-  }
-  RUN(add(at, hi));
-  return flush();
+  DYB_REQUIRE(!ema && !g2 && !g3, DYB_ERR_UNSUPPORTED);
+  return walk_gaps(S, lo, hi, [&](const DybFwSegs& t) {
+    return dyb_adam_step_segs(S.theta, S.grads, S.adam_m, S.adam_v, (float)S.beta1, (float)S.beta2, ss, bc, (float)S.eps, t, s);
+  });
 }
-// this step's Adam bias corrections for every replica of the current scope (step counts advance HERE), kept for weight_update(adam) and
-// written into each replica's adam_sc on `st` for the weight-gradient epilogues that apply Adam themselves
-static int adam_prepare(Stepper& S, hipStream_t st) {
+// this step's Adam bias corrections of every replica of the current scope, by physical replica (each has its own step count, which
+// advances HERE; adam_t keeps the largest)
+static void adam_corrections(Stepper& S, float* ss, float* bc) {
   const DybRep& R = dyb_rep_current();
-  for (int r = 0; r < DYB_MAX_REPLICAS; ++r) { S.pre_ss[r] = 0.f; S.pre_bc[r] = 1.f; }
+  for (int r = 0; r < DYB_MAX_REPLICAS; ++r) { ss[r] = 0.f; bc[r] = 1.f; }
   for (int i = 0; i < R.n; ++i) {
     const int r = dyb_rep_phys(R, i);
     const double t = (double)(++S.adam_t_rep[r]);
-    S.pre_ss[r] = (float)(S.lr / (1.0 - pow(S.beta1, t)));
-    S.pre_bc[r] = (float)sqrt(1.0 - pow(S.beta2, t));
+    ss[r] = (float)(S.lr / (1.0 - pow(S.beta1, t)));
+    bc[r] = (float)sqrt(1.0 - pow(S.beta2, t));
     if (S.adam_t_rep[r] > S.adam_t) S.adam_t = S.adam_t_rep[r];
   }
+}
+// the corrections fixed BEFORE the outer backward: kept for weight_update(adam) and written into each replica's adam_sc on `st` for the
+// weight-gradient epilogues that apply Adam themselves ("fuse_adam")
+static int adam_prepare(Stepper& S, hipStream_t st) {
+  adam_corrections(S, S.pre_ss, S.pre_bc);
   S.adam_prepared = true;
   return dyb_adam_write_scalars(S.adam_sc, S.pre_ss, S.pre_bc, st);
 }
-// Adam on every replica of the current launch scope, each with its own step count (bias corrections per physical replica)
+// one arena range of the weight update U on stream `s`
+static int update_range(Stepper& S, const Stepper::Upd& U, size_t lo, size_t hi, hipStream_t s) {
+  if (!U.adam) return fastweight_range(S, U.p, U.out, U.g2, U.g3, lo, hi, s);
+  // update_teacher (base_adaptor.py:193-201) of the same range: inside the Adam pass ("fuse_ema"), or right behind it
+  const bool fe = U.ema && S.fuse_ema;
+  RUN(adam_range(S, U.g2, U.g3, U.ss, U.bc, lo, hi, s, fe));
+  if (U.ema && !fe) RUN(dyb_ema_update(S.teacher + lo, S.theta + lo, (float)S.alpha, hi - lo, s));
+  return DYB_OK;
+}
 // the deferred last range of a ranged weight update (see weight_update): issued from inside the consuming forward at layer3
 static int late_update(void* user) {
   Stepper& S = *reinterpret_cast<Stepper*>(user);
   Stepper::LateUpd& L = S.late;
   DybRepScope scope(L.scope);
-  const size_t lo = S.grp_bounds[1], n = S.n_params - lo;
   HIPOK(hipStreamWaitEvent(L.aux, S.gates.mid, 0));
-  DybStreamCapScope cap(S.upd_blocks > 0 ? (S.upd_blocks / L.scope.n > 0 ? S.upd_blocks / L.scope.n : 1) : 0);
-  const float *g2 = L.g2 ? L.g2 + lo : nullptr, *g3 = L.g3 ? L.g3 + lo : nullptr;
-  if (L.adam) {
-    const bool fe = L.ema && S.fuse_ema;
-    RUN(adam_range(S, g2 ? L.g2 : nullptr, g3 ? L.g3 : nullptr, L.ss, L.bc, lo, lo + n, L.aux, fe));
-    if (L.ema && !fe) RUN(dyb_ema_update(S.teacher + lo, S.theta + lo, (float)S.alpha, n, L.aux));
-  } else {
-    RUN(fastweight_range(S, L.p, L.out, g2 ? L.g2 : nullptr, g3 ? L.g3 : nullptr, lo, lo + n, L.aux));
-  }
+  RUN(update_range(S, L.u, S.grp_bounds[1], S.n_params, L.aux));
   HIPOK(hipEventRecord(S.gates.ev[1], L.aux));
   S.gates.late = nullptr;
   return DYB_OK;
 }
-// One weight update over the whole arena - the fast-weight step out = p - fastlr * grads (adam = false) or Adam in place on theta -
+// One weight update over the whole arena - the fast-weight step out = p - fastlr * grads (adam = false) or Adam in place on theta, each
+// replica of the launch scope with its own bias corrections -
 // as one launch on `st`, or (upd_overlap, replica groups with an auxiliary stream) by arena ranges: [0, layer3) on `st`, [layer3,
 // layer4) and [layer4, end) on `aux` behind everything `st` has issued, each followed by its gate event; the next pass_forward waits
 // for them where it first reads those weights.
@@ -1003,71 +858,48 @@ static int weight_update(Stepper& S, bool adam, const float* p, float* out, hipS
   // its events would satisfy later waits with stale weights - settle it first
   if (S.gates_pending) RUN(settle_update(S, st));
   DYB_REQUIRE(!S.gates.late, DYB_ERR_LAUNCH);
-  const DybRep& R = dyb_rep_current();
-  const float *g2 = S.lvl_g2, *g3 = S.lvl_g3;        // further gradient arenas of the level just differentiated (full term set), consumed here
+  Stepper::Upd U;
+  U.adam = adam; U.ema = ema; U.p = p; U.out = out;
+  U.g2 = S.lvl_g2; U.g3 = S.lvl_g3;                  // further gradient arenas of the level just differentiated (full term set), consumed here
   S.lvl_g2 = S.lvl_g3 = nullptr;
   // the spans this level's weight gradients turned into fast weights themselves ("fuse_fast"): taken over, sorted, for this update only
   S.upd_spans.clear();
   S.upd_spans.swap(S.fused_spans);
   std::sort(S.upd_spans.begin(), S.upd_spans.end(), [](const DybSpan& a, const DybSpan& b) { return a.off < b.off; });
   S.fused_spans.clear();
-  float ss[DYB_MAX_REPLICAS], bc[DYB_MAX_REPLICAS];
   if (adam && S.adam_prepared) {                       // fixed before the outer backward (adam_prepare): the epilogues used the same numbers
-    for (int r = 0; r < DYB_MAX_REPLICAS; ++r) { ss[r] = S.pre_ss[r]; bc[r] = S.pre_bc[r]; }
+    for (int r = 0; r < DYB_MAX_REPLICAS; ++r) { U.ss[r] = S.pre_ss[r]; U.bc[r] = S.pre_bc[r]; }
     S.adam_prepared = false;
   } else if (adam) {
-    for (int r = 0; r < DYB_MAX_REPLICAS; ++r) { ss[r] = 0.f; bc[r] = 1.f; }
-    for (int i = 0; i < R.n; ++i) {
-      const int r = dyb_rep_phys(R, i);
-      const double t = (double)(++S.adam_t_rep[r]);
-      ss[r] = (float)(S.lr / (1.0 - pow(S.beta1, t)));
-      bc[r] = (float)sqrt(1.0 - pow(S.beta2, t));
-      if (S.adam_t_rep[r] > S.adam_t) S.adam_t = S.adam_t_rep[r];
-    }
+    adam_corrections(S, U.ss, U.bc);
   }
-  auto range = [&](size_t lo, size_t hi, hipStream_t s) -> int {
-    if (adam) {
-      // update_teacher (base_adaptor.py:193-201) of the same range: inside the Adam pass ("fuse_ema"), or right behind it
-      const bool fe = ema && S.fuse_ema;
-      RUN(adam_range(S, g2, g3, ss, bc, lo, hi, s, fe));
-      if (ema && !fe) RUN(dyb_ema_update(S.teacher + lo, S.theta + lo, (float)S.alpha, hi - lo, s));
-      return DYB_OK;
-    }
-    return fastweight_range(S, p, out, g2, g3, lo, hi, s);
-  };
-  const bool ranged = ranged_form(S, st, aux);
-  if (!ranged) {
+  if (!ranged_form(S, st, aux)) {
     if (S.defer_pending) {         // (a switch flipped between the backward and its update) the pass reads / rewrites what the deferred set writes
       HIPOK(hipStreamWaitEvent(st, S.ev->l4, 0));
       HIPOK(hipStreamWaitEvent(st, S.ev->reg, 0));
       S.defer_pending = false;
     }
-    return range(0, S.n_params, st);
+    return update_range(S, U, 0, S.n_params, st);
   }
   // the consuming forward waits for the level's deferred weight gradients too.  The ranged pass of [layer4, end) below / in late_update
   // writes the spans of that arena range those launches did NOT update themselves (and, without fused epilogues, reads their gradients):
   // it is issued on `aux`, an in-order stream, behind them - keep it there.
   S.gates.l4 = S.defer_pending ? S.ev->l4 : nullptr;
   S.gates.reg = S.defer_pending ? S.ev->reg : nullptr;
-  RUN(range(0, S.grp_bounds[0], st));
+  RUN(update_range(S, U, 0, S.grp_bounds[0], st));
   HIPOK(hipEventRecord(S.e_upd, st));                 // the gradients' main-stream writers (and the first range) are behind this point
   HIPOK(hipStreamWaitEvent(aux, S.e_upd, 0));
-  {
-    DybStreamCapScope cap(S.upd_blocks > 0 ? (S.upd_blocks / R.n > 0 ? S.upd_blocks / R.n : 1) : 0);   // upd_blocks = workgroups over ALL replicas
-    RUN(range(S.grp_bounds[0], S.grp_bounds[1], aux));
-    HIPOK(hipEventRecord(S.gates.ev[0], aux));
-    if (S.upd_late) {
-      // the last range waits until the forward that consumes it reaches layer3 (gates.late, called from inside that forward)
-      S.late.S = &S; S.late.adam = adam; S.late.ema = ema; S.late.p = p; S.late.out = out; S.late.aux = aux; S.late.scope = R;
-      S.late.g2 = g2; S.late.g3 = g3;
-      for (int r = 0; r < DYB_MAX_REPLICAS; ++r) { S.late.ss[r] = ss[r]; S.late.bc[r] = bc[r]; }
-      S.gates.late = &late_update;
-      S.gates.user = &S;
-    } else {
-      S.gates.late = nullptr;
-      RUN(range(S.grp_bounds[1], S.n_params, aux));
-      HIPOK(hipEventRecord(S.gates.ev[1], aux));
-    }
+  RUN(update_range(S, U, S.grp_bounds[0], S.grp_bounds[1], aux));
+  HIPOK(hipEventRecord(S.gates.ev[0], aux));
+  if (S.upd_late) {
+    // the last range waits until the forward that consumes it reaches layer3 (gates.late, called from inside that forward)
+    S.late.u = U; S.late.aux = aux; S.late.scope = dyb_rep_current();
+    S.gates.late = &late_update;
+    S.gates.user = &S;
+  } else {
+    S.gates.late = nullptr;
+    RUN(update_range(S, U, S.grp_bounds[1], S.n_params, aux));
+    HIPOK(hipEventRecord(S.gates.ev[1], aux));
   }
   S.gates_pending = true;
   return DYB_OK;
@@ -1094,109 +926,6 @@ static int settle_update(Stepper& S, hipStream_t st) {
   S.gates_pending = false;
   return DYB_OK;
 }
-static int adam_scope(Stepper& S, hipStream_t st) { return weight_update(S, true, nullptr, nullptr, st, nullptr); }
-static int adapt_frame_impl(Stepper& S, const float* image, const float* kp2d, const float* gt_pose, const float* gt_betas,
-                            const long long* gender, int record_slot, int loss_slot, hipStream_t st, hipStream_t aux,
-                            hipStream_t side) {
-  const bool metrics = S.metrics != 0;
-  DYB_REQUIRE(!metrics || (gt_pose && gt_betas && gender), DYB_ERR_ARG);
-  S.out_in_main = false;                                  // this frame's final inference goes to `fin` (ADVICE r5: reset at every entry point)
-  if (!S.use_side || side == st) side = nullptr;
-  const int K = S.inner_step;
-  const size_t n = S.n_params;
-  float* losslog = (S.loss_log && loss_slot >= 0 && loss_slot < S.loss_capacity) ? S.loss_log + (size_t)loss_slot * 4 * (K + 1) : nullptr;
-  int slot = record_slot;
-
-  if (metrics) {
-    // the ground-truth meshes only feed metric kernels: on the side stream when there is one, behind the previous frame's
-    // tail (which still reads the buffers) - both are issued below, once this frame's first level is in the main queue
-    if (side) {
-      S.gtjob.on = true; S.gtjob.pose = gt_pose; S.gtjob.betas = gt_betas;
-    } else {
-      RUN(gt_meshes(S, gt_pose, gt_betas, st));
-    }
-  }
-  // the main stream waits for the meshes only where it first reads them (the record after inner step 0): at the top of
-  // the frame the side stream is still busy with the previous frame's final forward, and waiting there stalled the main
-  // chain for that whole tail (1.1 ms per frame in the kernel trace)
-  bool gt_waited = !(metrics && side);
-  RUN(side_wait(S));                                  // (idle long since: the previous frame posted its job at its first level)
-  HostTimer t_all(S.h_total);
-  ++S.h_frames;
-  const float* cur = S.theta;                    // clone(): the learner starts as an alias of theta
-  for (int i = 0; i <= K; ++i) {                 // i < K: lower level + adapt; i == K: upper level
-    {
-      HostTimer t(S.h_fwd);
-      RUN(pass_forward(S, S.main, cur, image, st));
-    }
-    {
-      HostTimer th(S.h_head);
-      RUN(pass_frame_head(S, S.main, kp2d, st));
-      if (losslog) {
-        hipLaunchKernelGGL(copy4_kernel, dim3(1, 1, dyb_rep_current().n), dim3(64), 0, st, (const float*)S.main.losses, losslog + 4 * i,
-                           dyb_rep_current());
-        DYB_CHECK_LAUNCH();
-      }
-      // inference() after inner step i-1 = this level's forward (same weights, same image: dynaboa_benchmark.py:142)
-      if (metrics && S.eval_lower && i > 0) {
-        if (!gt_waited) {
-          RUN(side_wait(S));                          // e_gt has been recorded
-          HIPOK(hipStreamWaitEvent(st, S.e_gt, 0));
-          gt_waited = true;
-        }
-        RUN(record_metrics(S, S.main, gender, slot++, st));
-      }
-    }
-    // the next level's weights: the other fast buffer when the weight gradients may write them while data gradients still read `cur`
-    float* nxt = (S.fuse_fast && S.theta_fast2 && cur == S.theta_fast) ? S.theta_fast2 : S.theta_fast;
-    {
-      HostTimer t(S.h_bwd);
-      S.fused_spans.clear();
-      DybWgradUpdate upd{};
-      if (i < K && S.fuse_fast && S.theta_fast2) {
-        upd = DybWgradUpdate{S.grads, n * sizeof(float), cur, nxt, (float)S.fastlr, &S.fused_spans};
-      } else if (i == K && S.fuse_adam && cur != S.theta && !side && S.nrep > 1) {
-        // the outer level is differentiated at the fast weights: theta has no reader until the final inference - Adam may be applied
-        // layer by layer as the weight gradients finish (replica groups: no side stream whose tail would still read theta)
-        RUN(adam_prepare(S, st));
-        upd = DybWgradUpdate{S.grads, n * sizeof(float), S.theta, S.theta, 0.f, &S.fused_spans};
-        upd.adam_m = S.adam_m; upd.adam_v = S.adam_v; upd.adam_sc = S.adam_sc;
-        upd.b1 = (float)S.beta1; upd.b2 = (float)S.beta2; upd.eps = (float)S.eps;
-      }
-      DybWgradUpdateScope fuse(upd);
-      RUN(pass_backward(S, S.main, cur, S.grads, st, aux));
-    }
-    if (i == 0 && side) {
-      HostTimer t(S.h_tail);
-      RUN(side_post(S, side));
-    }
-    if (i < K) {
-      HostTimer t(S.h_update);
-      RUN(weight_update(S, false, cur, nxt, st, aux));
-      cur = nxt;
-    }
-  }
-  HostTimer t_tail(S.h_tail);
-  // optimizer.step(): theta is about to change in place - the previous frame's tail on the side stream reads it
-  RUN(side_wait(S));
-  if (S.side_pending) {
-    HIPOK(hipStreamWaitEvent(st, S.e_side, 0));
-    S.side_pending = false;
-  }
-  RUN(weight_update(S, true, nullptr, nullptr, st, side ? nullptr : aux));
-  // final inference() with the updated weights (dynaboa_benchmark.py:156): in line, or - with a side stream - owed to the
-  // next call / dyb_stepper_join (the caller keeps this frame's inputs alive until then)
-  if (side) {
-    HIPOK(hipEventRecord(S.e_theta, st));
-    S.tail.on = true; S.tail.image = image; S.tail.gender = gender; S.tail.slot = slot++; S.tail.metrics = metrics;
-    S.tail_stream = side;
-    return DYB_OK;
-  }
-  RUN(pass_forward(S, S.fin, S.theta, image, st));
-  RUN(settle_update(S, st));                         // (consumed by the forward above; a no-op unless that changes)
-  if (metrics) RUN(record_metrics(S, S.fin, gender, slot++, st));
-  return DYB_OK;
-}
 // ---- the full loss set -------------------------------------------------------------------------------------------------
 // gradient of (frame loss [+ external terms]) or of external terms alone w.r.t. theta through pass P
 static int pass_backward_ext(Stepper& S, Pass& P, const float* theta, float* grads, bool frame_loss, const float* e_rot,
@@ -1216,10 +945,15 @@ enum { IN_IMAGE = 0, IN_KP, IN_GT_POSE, IN_GT_BETAS, IN_GENDER, IN_HIST_IMAGE, I
 // copy `nk` inputs (kinds k0 .. k0+nk-1 in IN_* order) of every replica of the current scope from the callers' separate tensors
 // into the replicas' staging areas, one launch: src[(kind - k0) * ld + physical replica] (NULL: nothing to copy)
 static int stage_inputs(Stepper& S, const void* const* src, int ld, int k0, int nk, hipStream_t st);
-struct FullCtx {
-  const void* in[IN_COUNT];
-  float* losslog;       // this frame's rows
-  int level_row;
+// what the levels of one frame step share
+struct LevelCtx {
+  const void* in[IN_COUNT];   // the frame's inputs: the callers' tensors (one sequence) or the staging areas; NULL = absent
+  float* losslog;             // this frame's log rows (NULL: not logged)
+  hipStream_t side;           // the side stream this frame step uses (frame-loss set, one sequence), or NULL
+  // the main stream waits for the ground-truth meshes only where it first reads them (the record after inner step 0): at the top of
+  // the frame the side stream is still busy with the previous frame's final forward, and waiting there stalled the main
+  // chain for that whole tail (1.1 ms per frame in the kernel trace)
+  bool gt_waited;
 };
 // A level that forked onto the pass streams and fails before its joins must not return with work still queued there against the
 // stepper's arenas: the caller's stream is ordered behind the CURRENT tails of both pass streams on every early return, so a
@@ -1234,18 +968,23 @@ struct ParTailGuard {
     if (sC != st && hipEventRecord(eC, sC) == hipSuccess) (void)hipStreamWaitEvent(st, eC, 0);
   }
 };
-// one level (reference base_adaptor.py:222-317 lower / upper_level_adaptation) at weights `cur` through pass P: loss terms,
-// log row, and the gradient of the level total w.r.t. `cur` in S.grads
+// the weight gradients' fused update epilogues ("fuse_fast", "fuse_adam") exist for single-pass levels: never with the full term set
+static bool fused_epilogues(const Stepper& S) { return !S.full; }
+// One level (reference base_adaptor.py:222-317 lower / upper_level_adaptation) at weights `cur` through pass P: forward, frame head,
+// the metric record of the inference this forward stands for (record_slot >= 0), the terms of the full set that are enabled, the log
+// row (frame-loss set: the head's 4 floats; full set: 16), and the gradient of the level total w.r.t. `cur` in S.grads (+ S.lvl_g2 /
+// lvl_g3, which the weight update that follows sums).  With no term enabled these are the launches of the frame-loss set exactly.
+// nxt: where a lower level's fused epilogues write the next fast weights.
 // have_fwd: P already holds the forward of (cur, this frame's image) - the dynamic loop hands the previous step's final inference on
-static int full_level(Stepper& S, FullCtx& C, Pass& P, const float* cur, bool upper, int level_index, hipStream_t st, hipStream_t aux,
-                      bool have_fwd = false) {
+static int level(Stepper& S, LevelCtx& C, Pass& P, const float* cur, float* nxt, bool upper, int level_index, int record_slot, hipStream_t st,
+                 hipStream_t aux, bool have_fwd = false) {
   const int B = S.B;
   const float* image = (const float*)C.in[IN_IMAGE];
   const float* kp = (const float*)C.in[IN_KP];
-  const bool temporal = upper ? S.temporal_upper != 0 : S.temporal_lower != 0;
+  const bool temporal = S.full && (upper ? S.temporal_upper != 0 : S.temporal_lower != 0);
   const bool teacher = temporal && S.use_teacher && S.teacher;
   const bool motion = temporal && S.use_motion && C.in[IN_HIST_IMAGE] && C.in[IN_HIST_KP];
-  const bool label = (upper ? S.mix_upper : S.mix_lower) != 0;
+  const bool label = S.full && (upper ? S.mix_upper : S.mix_lower) != 0;
   // One sequence: the history pass and the exemplar pass go to streams of their own.  Dependencies (events par_ev[]): both wait for
   // the weights (0: recorded on the chain where the level starts); the motion term (chain) needs the history forward (1) and leaves
   // the history pass's head gradients (2) for its backward; the chain's log row reads the label term's values (4); the weight update
@@ -1271,8 +1010,28 @@ static int full_level(Stepper& S, FullCtx& C, Pass& P, const float* cur, bool up
     if (label) HIPOK(hipStreamWaitEvent(sC, S.par_ev[0], 0));
   }
   ParTailGuard tails{st, sB, sC, S.par_ev[6], S.par_ev[7], par};
-  if (!have_fwd) RUN(pass_forward(S, P, cur, image, st));
-  RUN(pass_frame_head(S, P, kp, st));
+  if (!have_fwd) {
+    HostTimer t(S.h_fwd);
+    RUN(pass_forward(S, P, cur, image, st));
+  }
+  {
+    HostTimer th(S.h_head);
+    RUN(pass_frame_head(S, P, kp, st));
+    if (C.losslog && !S.full) {
+      hipLaunchKernelGGL(copy4_kernel, dim3(1, 1, dyb_rep_current().n), dim3(64), 0, st, (const float*)P.losses, C.losslog + 4 * level_index,
+                         dyb_rep_current());
+      DYB_CHECK_LAUNCH();
+    }
+    // inference() after the previous inner step = this level's forward (same weights, same image: dynaboa_benchmark.py:142); the record
+    // only reads the pass's forward products, which nothing later in the level writes
+    if (record_slot >= 0) {
+      if (!C.gt_waited) {
+        HIPOK(hipStreamWaitEvent(st, S.e_gt, 0));
+        C.gt_waited = true;
+      }
+      RUN(record_metrics(S, P, (const long long*)C.in[IN_GENDER], record_slot, st));
+    }
+  }
   const float* rot = P.acts + S.off_rot;
   const float* state = P.acts + S.off_state;
   if (ranged_before) {
@@ -1372,18 +1131,35 @@ static int full_level(Stepper& S, FullCtx& C, Pass& P, const float* cur, bool up
     DYB_REQUIRE(C.in[IN_EX_IMG] && C.in[IN_EX_KP] && C.in[IN_EX_POSE] && C.in[IN_EX_BETAS] && C.in[IN_EX_POSE3D], DYB_ERR_ARG);
     RUN(label_pass_forward_and_term(st, true));
   }
-  if (C.losslog) {
+  if (C.losslog && S.full) {
     if (par && label) HIPOK(hipStreamWaitEvent(st, S.par_ev[4], 0));          // the row reads the label term's values
     hipLaunchKernelGGL(level_log_kernel, dim3(1, 1, dyb_rep_current().n), dim3(64), 0, st, (const float*)P.losses,
                        teacher ? (const float*)S.vals_t : nullptr, motion ? (const float*)S.vals_m : nullptr,
                        label ? (const float*)S.vals_l : nullptr, (float)S.teacher_w, (float)S.motion_w, (float)S.label_w,
-                       C.losslog + 16 * C.level_row, dyb_rep_current());
+                       C.losslog + 16 * level_index, dyb_rep_current());
     DYB_CHECK_LAUNCH();
-    ++C.level_row;
   }
   // gradient of the level total: image pass (+ its external terms), history pass, exemplar pass
-  RUN(pass_backward_ext(S, P, cur, S.grads, true, ext ? S.ext_rot : nullptr, ext ? S.ext_shape : nullptr, ext ? S.ext_cam : nullptr,
-                        ext ? S.ext_joints : nullptr, st, aux));
+  {
+    HostTimer t(S.h_bwd);
+    // The weight gradients' fused update epilogues (DybWgradUpdateScope, igemm_conv.hip).  Lower level, "fuse_fast": theta_next = cur -
+    // fastlr * g straight from the accumulators.  Upper level, "fuse_adam": it is
+    // differentiated at the fast weights, so theta has no reader until the final inference - Adam may be applied layer by layer as the
+    // weight gradients finish (replica groups: no side stream whose tail would still read theta)
+    S.fused_spans.clear();
+    DybWgradUpdate upd{};
+    if (fused_epilogues(S) && !upper && S.fuse_fast && S.theta_fast2) {
+      upd = DybWgradUpdate{S.grads, S.n_params * sizeof(float), cur, nxt, (float)S.fastlr, &S.fused_spans};
+    } else if (fused_epilogues(S) && upper && S.fuse_adam && cur != S.theta && !C.side && S.nrep > 1) {
+      RUN(adam_prepare(S, st));
+      upd = DybWgradUpdate{S.grads, S.n_params * sizeof(float), S.theta, S.theta, 0.f, &S.fused_spans};
+      upd.adam_m = S.adam_m; upd.adam_v = S.adam_v; upd.adam_sc = S.adam_sc;
+      upd.b1 = (float)S.beta1; upd.b2 = (float)S.beta2; upd.eps = (float)S.eps;
+    }
+    DybWgradUpdateScope fuse(upd);
+    RUN(pass_backward_ext(S, P, cur, S.grads, true, ext ? S.ext_rot : nullptr, ext ? S.ext_shape : nullptr, ext ? S.ext_cam : nullptr,
+                          ext ? S.ext_joints : nullptr, st, aux));
+  }
   // (the level's gradient = (image pass + history pass) + exemplar pass: the passes keep their own arenas and the weight update that
   // follows every level adds them while it reads them - no accumulation passes)
   S.lvl_g2 = S.lvl_g3 = nullptr;
@@ -1401,8 +1177,9 @@ static int full_level(Stepper& S, FullCtx& C, Pass& P, const float* cur, bool up
   tails.armed = false;                                    // both pass streams have been joined above
   return DYB_OK;
 }
-static int adam_and_teacher(Stepper& S, hipStream_t st, hipStream_t aux) {
-  return weight_update(S, true, nullptr, nullptr, st, aux, S.use_teacher && S.teacher);      // Adam, then the teacher's EMA (base_adaptor.py:193-201)
+// optimizer.step() on every replica of the launch scope, then the teacher's EMA (full set; base_adaptor.py:193-201)
+static int outer_update(Stepper& S, hipStream_t st, hipStream_t aux) {
+  return weight_update(S, true, nullptr, nullptr, st, aux, S.full && S.use_teacher && S.teacher);
 }
 // features of two forwards -> 15 cosines per replica of the current scope (device log row + host-visible copy); cos12[r] (indexed
 // by PHYSICAL replica) = cos[12] read from the host copy
@@ -1497,212 +1274,222 @@ static int active_set(const Stepper& S, int* idx) {
   return S.nrep;
 }
 
-// Adaptor.adaptation with the reference's full term set (dynaboa_benchmark.py:126-193) for every replica of the current launch
-// scope (one replica without a scope).  C.in: the frame's inputs - the callers' tensors (one replica) or the staging areas.
+// One adapted frame - Adaptor.adaptation (reference dynaboa_benchmark.py:126-193) - for every replica of the current launch scope (one
+// replica without a scope), with the frame-loss set or, S.full, the reference's full term set.  C.in: the frame's inputs; gt_pose
+// [B][72] / gt_betas [B][10] / gender [B] (int64) feed the metric records only (NULL with metrics = 0).  Records: inner_step
+// (eval_lower) + 1 slots from record_slot in schedule order - after inner step 0, 1, ..., then the final one (+ one per step of the
+// dynamic loop); loss rows: one per level at loss_slot (4 floats {s2d, shape prior, pose prior, weighted total}, full set: 16).
+// side (frame-loss set, one sequence; may be NULL): stream for the final no-grad forward and its metrics, overlapped with the next
+// frame's first level; the call orders the weight hazards itself.
 // extra[r] (physical replica) receives the number of dynamic-loop iterations replica r took: the gate is evaluated per replica,
 // and a replica whose feature 12 has stopped moving LEAVES the launch set of the remaining iterations (the others are not held
 // back by it, and it does not take Adam steps the reference would not have taken).
-static int adapt_full_impl(Stepper& S, FullCtx& C, int record_slot, int loss_slot, int* extra, hipStream_t st, hipStream_t aux) {
+static int frame_step(Stepper& S, LevelCtx& C, int record_slot, int loss_slot, int* extra, hipStream_t st, hipStream_t aux, hipStream_t side) {
   const bool metrics = S.metrics != 0;
-  S.out_in_main = false;                                  // (set again below only when a shared-forward step of the dynamic loop ends in `main`)
   DYB_REQUIRE(C.in[IN_IMAGE] && C.in[IN_KP], DYB_ERR_ARG);
   DYB_REQUIRE(!metrics || (C.in[IN_GT_POSE] && C.in[IN_GT_BETAS] && C.in[IN_GENDER]), DYB_ERR_ARG);
+  S.out_in_main = false;                                  // this frame's final inference goes to `fin` (ADVICE r5: reset at every entry point)
+  if (!S.use_side || side == st) side = nullptr;
+  const float* image = (const float*)C.in[IN_IMAGE];
   const long long* gender = (const long long*)C.in[IN_GENDER];
   const int K = S.inner_step;
-  const int rows = K + 1 + (S.dynamic ? S.optim_steps : 0);
-  C.losslog = (S.loss_log && loss_slot >= 0 && loss_slot < S.loss_capacity) ? S.loss_log + (size_t)loss_slot * 16 * rows : nullptr;
-  C.level_row = 0;
+  const int rows = K + 1 + (S.full && S.dynamic ? S.optim_steps : 0);
+  C.losslog = (S.loss_log && loss_slot >= 0 && loss_slot < S.loss_capacity) ? S.loss_log + (size_t)loss_slot * (S.full ? 16 : 4) * rows : nullptr;
+  C.side = side;
   int slot = record_slot;
   const DybRep outer = dyb_rep_current();                 // (copy: nested scopes below replace the thread's current one)
   for (int i = 0; i < outer.n; ++i) extra[dyb_rep_phys(outer, i)] = 0;
-  if (metrics) RUN(gt_meshes(S, (const float*)C.in[IN_GT_POSE], (const float*)C.in[IN_GT_BETAS], st));
-  const float* cur = S.theta;
-  for (int i = 0; i <= K; ++i) {
-    Pass& P = (i == 0 && S.dynamic) ? S.lvl0 : S.main;
-    RUN(full_level(S, C, P, cur, i == K, i, st, aux));
-    // (the level's gradient is complete; the metric record of the previous inner step reads this level's forward)
-    if (metrics && S.eval_lower && i > 0) RUN(record_metrics(S, P, gender, slot++, st));
+  if (metrics) {
+    // the ground-truth meshes only feed metric kernels: on the side stream when there is one, behind the previous frame's
+    // tail (which still reads the buffers) - both are issued below, once this frame's first level is in the main queue
+    if (side) {
+      S.gtjob.on = true; S.gtjob.pose = (const float*)C.in[IN_GT_POSE]; S.gtjob.betas = (const float*)C.in[IN_GT_BETAS];
+    } else {
+      RUN(gt_meshes(S, (const float*)C.in[IN_GT_POSE], (const float*)C.in[IN_GT_BETAS], st));
+    }
+  }
+  C.gt_waited = !(metrics && side);
+  HostTimer t_all(S.h_total);
+  ++S.h_frames;
+  const float* cur = S.theta;                    // clone(): the learner starts as an alias of theta
+  for (int i = 0; i <= K; ++i) {                 // i < K: lower level + adapt; i == K: upper level
+    Pass& P = (i == 0 && S.full && S.dynamic) ? S.lvl0 : S.main;     // level 0's features gate the dynamic loop
+    // the next level's weights: the other fast buffer when the weight gradients may write them while data gradients still read `cur`
+    float* nxt = (fused_epilogues(S) && S.fuse_fast && S.theta_fast2 && cur == S.theta_fast) ? S.theta_fast2 : S.theta_fast;
+    RUN(level(S, C, P, cur, nxt, i == K, i, (metrics && S.eval_lower && i > 0) ? slot++ : -1, st, aux));
+    if (i == 0 && side) {
+      HostTimer t(S.h_tail);
+      RUN(issue_side_work(S, side));
+    }
     if (i < K) {
-      RUN(weight_update(S, false, cur, S.theta_fast, st, aux));
-      cur = S.theta_fast;
+      HostTimer t(S.h_update);
+      RUN(weight_update(S, false, cur, nxt, st, aux));
+      cur = nxt;
     }
   }
-  RUN(adam_and_teacher(S, st, aux));
-  const float* image = (const float*)C.in[IN_IMAGE];
-  RUN(pass_forward(S, S.fin, S.theta, image, st));
-  if (metrics) RUN(record_metrics(S, S.fin, gender, slot++, st));
-  if (S.dynamic) {
-    // dynaboa_benchmark.py:161-192: compare features of the un-adapted and the adapted forward; while feature 12 still
-    // moves, repeat the upper level on the model itself (at most optim_steps times)
-    float* glog = (S.gate_log && loss_slot >= 0 && loss_slot < S.loss_capacity) ? S.gate_log + (size_t)loss_slot * (1 + S.optim_steps) * 16 : nullptr;
-    DYB_REQUIRE(glog, DYB_ERR_ARG);
-    float cos12[DYB_MAX_REPLICAS];
-    RUN(gate_cosine(S, S.lvl0.acts, S.fin.acts, glog, cos12, st));     // (inner_step 0: the upper level's own forward is lvl0)
-    int cont[DYB_MAX_REPLICAS], ncont = 0;
-    for (int i = 0; i < outer.n; ++i)
-      if (1.f - cos12[dyb_rep_phys(outer, i)] > (float)S.cos_thr) cont[ncont++] = dyb_rep_phys(outer, i);
-    int step = 0;
-    Pass* post = &S.fin;                                   // where the latest final inference lives
-    S.out_in_main = false;
-    while (ncont > 0) {
-      ++step;
-      if (step > S.optim_steps) {
-        for (int i = 0; i < ncont; ++i) extra[cont[i]] = S.optim_steps + 1;
-        break;
-      }
-      {
-        // the replicas still adapting get a scope of their own (one replica without replica machinery: the scope it came with)
-        DybRep sub = outer;
-        dyb_rep_set_map(sub, cont, ncont);
-        DybRepScope scope(sub);
-        C.level_row = K + step;
-        // The upper level of this step starts with a forward at (theta, this image) - exactly the final inference the previous step
-        // ended with (same weights, same image, deterministic kernels): it is not repeated.  `up` = that forward's products with the
-        // chain's gradient buffers; the new final inference goes to the other activation arena (the gate compares the two), and the
-        // two arenas swap roles every step ("share_dyn_fwd"; 0: the literal two forwards per step).
-        if (S.share_dyn_fwd) {
-          Pass up = S.main;
-          up.acts = post->acts; up.verts = post->verts; up.joints = post->joints; up.saved = post->saved; up.pred17 = post->pred17;
-          Pass* nxt = (post == &S.fin) ? &S.main : &S.fin;
-          RUN(full_level(S, C, up, S.theta, true, K + step, st, aux, true));
-          RUN(adam_and_teacher(S, st, aux));
-          RUN(pass_forward(S, *nxt, S.theta, image, st));
-          RUN(gate_cosine(S, up.acts, nxt->acts, glog + 16 * step, cos12, st));
-          if (metrics) RUN(record_metrics(S, *nxt, gender, slot, st));
-          post = nxt;
-          S.out_in_main = (post == &S.main);
-        } else {
-          RUN(full_level(S, C, S.main, S.theta, true, K + step, st, aux));
-          RUN(adam_and_teacher(S, st, aux));
-          RUN(pass_forward(S, S.fin, S.theta, image, st));
-          RUN(gate_cosine(S, S.main.acts, S.fin.acts, glog + 16 * step, cos12, st));
-          if (metrics) RUN(record_metrics(S, S.fin, gender, slot, st));
-        }
-      }
-      ++slot;
-      int m = 0;
-      for (int i = 0; i < ncont; ++i) {
-        extra[cont[i]] = step;
-        if (1.f - cos12[cont[i]] > (float)S.cos_thr) cont[m++] = cont[i];
-      }
-      ncont = m;
+  {
+    HostTimer t_tail(S.h_tail);
+    // optimizer.step(): theta is about to change in place - the previous frame's tail on the side stream reads it
+    if (S.side_pending) {
+      HIPOK(hipStreamWaitEvent(st, S.e_side, 0));
+      S.side_pending = false;
     }
+    RUN(outer_update(S, st, side ? nullptr : aux));
+    // final inference() with the updated weights (dynaboa_benchmark.py:156): in line, or - with a side stream - owed to the
+    // next call / dyb_stepper_join (the caller keeps this frame's inputs alive until then)
+    if (side) {
+      HIPOK(hipEventRecord(S.e_theta, st));
+      S.tail.on = true; S.tail.image = image; S.tail.gender = gender; S.tail.slot = slot++; S.tail.metrics = metrics;
+      S.tail_stream = side;
+      return DYB_OK;
+    }
+    RUN(pass_forward(S, S.fin, S.theta, image, st));
+    RUN(settle_update(S, st));                         // (consumed by the forward above; a no-op unless that changes)
+    if (metrics) RUN(record_metrics(S, S.fin, gender, slot++, st));
+  }
+  if (!(S.full && S.dynamic)) return DYB_OK;
+  // dynaboa_benchmark.py:161-192: compare features of the un-adapted and the adapted forward; while feature 12 still
+  // moves, repeat the upper level on the model itself (at most optim_steps times)
+  float* glog = (S.gate_log && loss_slot >= 0 && loss_slot < S.loss_capacity) ? S.gate_log + (size_t)loss_slot * (1 + S.optim_steps) * 16 : nullptr;
+  DYB_REQUIRE(glog, DYB_ERR_ARG);
+  float cos12[DYB_MAX_REPLICAS];
+  RUN(gate_cosine(S, S.lvl0.acts, S.fin.acts, glog, cos12, st));     // (inner_step 0: the upper level's own forward is lvl0)
+  int cont[DYB_MAX_REPLICAS], ncont = 0;
+  for (int i = 0; i < outer.n; ++i)
+    if (1.f - cos12[dyb_rep_phys(outer, i)] > (float)S.cos_thr) cont[ncont++] = dyb_rep_phys(outer, i);
+  int step = 0;
+  Pass* post = &S.fin;                                   // where the latest final inference lives
+  while (ncont > 0) {
+    ++step;
+    if (step > S.optim_steps) {
+      for (int i = 0; i < ncont; ++i) extra[cont[i]] = S.optim_steps + 1;
+      break;
+    }
+    {
+      // the replicas still adapting get a scope of their own (one replica without replica machinery: the scope it came with)
+      DybRep sub = outer;
+      dyb_rep_set_map(sub, cont, ncont);
+      DybRepScope scope(sub);
+      // The upper level of this step starts with a forward at (theta, this image) - exactly the final inference the previous step
+      // ended with (same weights, same image, deterministic kernels): it is not repeated.  `up` = that forward's products with the
+      // chain's gradient buffers; the new final inference goes to the other activation arena (the gate compares the two), and the
+      // two arenas swap roles every step ("share_dyn_fwd"; 0: the literal two forwards per step, main then fin).
+      Pass up = S.main;
+      Pass* nxt = &S.fin;
+      if (S.share_dyn_fwd) {
+        up.acts = post->acts; up.verts = post->verts; up.joints = post->joints; up.saved = post->saved; up.pred17 = post->pred17;
+        nxt = (post == &S.fin) ? &S.main : &S.fin;
+      }
+      RUN(level(S, C, up, S.theta, nullptr, true, K + step, -1, st, aux, S.share_dyn_fwd != 0));
+      RUN(outer_update(S, st, aux));
+      RUN(pass_forward(S, *nxt, S.theta, image, st));
+      RUN(gate_cosine(S, up.acts, nxt->acts, glog + 16 * step, cos12, st));
+      if (metrics) RUN(record_metrics(S, *nxt, gender, slot, st));
+      post = nxt;
+      S.out_in_main = (post == &S.main);
+    }
+    ++slot;
+    int m = 0;
+    for (int i = 0; i < ncont; ++i) {
+      extra[cont[i]] = step;
+      if (1.f - cos12[cont[i]] > (float)S.cos_thr) cont[m++] = cont[i];
+    }
+    ncont = m;
   }
   return DYB_OK;
 }
-// One sequence: inputs = HOST array of IN_COUNT device pointers (image, kp2d, gt_pose, gt_betas, gender, hist_image, hist_kp,
-// ex_img, ex_kp, ex_pose, ex_betas, ex_pose3d; the history pair NULL while there is no frame `interval` steps back, the exemplar
-// five NULL when a retrieval callback is set).  *extra_steps receives the number of dynamic-loop iterations taken.
-extern "C" int dyb_stepper_adapt_frame_full(void* stepper, const void* const* inputs, int record_slot, int loss_slot, int* extra_steps,
-                                            hipStream_t st, hipStream_t aux) {
-  Stepper* Sp = reinterpret_cast<Stepper*>(stepper);
-  DYB_REQUIRE(Sp && inputs && extra_steps, DYB_ERR_ARG);
-  Stepper& S = *Sp;
+// The frame step behind the four exported entry points.  inputs: HOST array of nk x replicas device pointers, kind-major -
+// inputs[kind * replicas + r], r the PHYSICAL replica (entries of inactive replicas are ignored) - in IN_* order: nk = 5 kinds with
+// the frame-loss set, 12 with the full term set.  One sequence: the step reads the callers' tensors; replicas (the active set,
+// dyb_stepper_set_active): every launch of the chain covers all of them, their inputs are staged into the workspace first, and
+// the terms must be alike for every active replica (lockstep).  extra_steps (may be NULL): `replicas` ints.
+static int adapt(Stepper& S, const void* const* inputs, int nk, int record_slot, int loss_slot, int* extra_steps, hipStream_t st,
+                 hipStream_t aux, hipStream_t side) {
   RUN(check_ready(S));
-  DYB_REQUIRE(S.full && S.nrep == 1 && S.B <= 16, DYB_ERR_UNSUPPORTED);
-  FullCtx C{};
-  for (int i = 0; i < IN_COUNT; ++i) C.in[i] = inputs[i];
-  int extra[DYB_MAX_REPLICAS];
-  RUN(adapt_full_impl(S, C, record_slot, loss_slot, extra, st, aux));
-  *extra_steps = extra[0];
-  return DYB_OK;
-}
-// The same for the stepper's replicas (the active set, dyb_stepper_set_active): every launch of the chain covers all of them,
-// teacher / history / exemplar passes included.  inputs: HOST array of IN_COUNT x replicas device pointers, kind-major -
-// inputs[kind * replicas + r], r the PHYSICAL replica (entries of inactive replicas are ignored); the history pair must be
-// present for all active replicas or for none; the exemplar five may be NULL when a per-replica retrieval callback
-// ("retrieve_rep_fn") is set.  theta / adam_m / adam_v / teacher are [replicas][param floats], records / loss_log / gate_log
-// [replicas][...], gate_host 16 floats per replica, feat5_out [replicas][B][2048].  extra_steps: `replicas` ints.
-extern "C" int dyb_stepper_adapt_frames_full(void* stepper, const void* const* inputs, int record_slot, int loss_slot, int* extra_steps,
-                                             hipStream_t st, hipStream_t aux) {
-  Stepper* Sp = reinterpret_cast<Stepper*>(stepper);
-  DYB_REQUIRE(Sp && inputs && extra_steps, DYB_ERR_ARG);
-  Stepper& S = *Sp;
-  RUN(check_ready(S));
-  DYB_REQUIRE(S.full && S.B <= 16, DYB_ERR_UNSUPPORTED);
-  if (S.nrep == 1) return dyb_stepper_adapt_frame_full(stepper, inputs, record_slot, loss_slot, extra_steps, st, aux);
-  int act[DYB_MAX_REPLICAS];
-  const int na = active_set(S, act);
+  DYB_REQUIRE((nk == IN_COUNT) == (S.full != 0) && (!S.full || S.B <= 16), DYB_ERR_UNSUPPORTED);
   const int n = S.nrep;
-  bool have_hist = false, have_ex = false, have_gt = false;
-  for (int i = 0; i < na; ++i) {
-    const int r = act[i];
-    DYB_REQUIRE(inputs[IN_IMAGE * n + r] && inputs[IN_KP * n + r], DYB_ERR_ARG);
-    const bool h = inputs[IN_HIST_IMAGE * n + r] && inputs[IN_HIST_KP * n + r];
-    const bool e = inputs[IN_EX_IMG * n + r] && inputs[IN_EX_KP * n + r] && inputs[IN_EX_POSE * n + r] && inputs[IN_EX_BETAS * n + r] &&
-                   inputs[IN_EX_POSE3D * n + r];
-    const bool gt = inputs[IN_GT_POSE * n + r] && inputs[IN_GT_BETAS * n + r] && inputs[IN_GENDER * n + r];
-    if (i == 0) { have_hist = h; have_ex = e; have_gt = gt; }
-    DYB_REQUIRE(h == have_hist && e == have_ex && gt == have_gt, DYB_ERR_UNSUPPORTED);     // lockstep: the same terms for every replica
+  int extra[DYB_MAX_REPLICAS] = {};
+  LevelCtx C{};
+  int rc;
+  if (n == 1) {
+    for (int k = 0; k < nk; ++k) C.in[k] = inputs[k];
+    rc = frame_step(S, C, record_slot, loss_slot, extra, st, aux, side);
+  } else {
+    // replicas + side stream: the owed final inference of frame f would read staging buffers the next call has already refilled,
+    // under the next frame's launch scope - replica groups run their tail in line
+    DYB_REQUIRE(!(S.use_side && side && side != st), DYB_ERR_UNSUPPORTED);
+    int act[DYB_MAX_REPLICAS];
+    const int na = active_set(S, act);
+    auto have = [&](int r, int k0, int k1) {
+      for (int k = k0; k <= k1; ++k)
+        if (k >= nk || !inputs[k * n + r]) return false;
+      return true;
+    };
+    const bool have_gt = have(act[0], IN_GT_POSE, IN_GENDER), have_hist = have(act[0], IN_HIST_IMAGE, IN_HIST_KP),
+               have_ex = have(act[0], IN_EX_IMG, IN_EX_POSE3D);
+    for (int i = 0; i < na; ++i) {
+      DYB_REQUIRE(have(act[i], IN_IMAGE, IN_KP), DYB_ERR_ARG);
+      DYB_REQUIRE(have(act[i], IN_GT_POSE, IN_GENDER) == have_gt && have(act[i], IN_HIST_IMAGE, IN_HIST_KP) == have_hist &&
+                  have(act[i], IN_EX_IMG, IN_EX_POSE3D) == have_ex, DYB_ERR_UNSUPPORTED);     // lockstep: the same terms for every replica
+    }
+    DybRep R{};
+    RUN(make_scope(S, act, na, &R));
+    DybRepScope scope(R);
+    RUN(stage_inputs(S, inputs, n, IN_IMAGE, 5, st));
+    if (have_hist) RUN(stage_inputs(S, inputs + (size_t)IN_HIST_IMAGE * n, n, IN_HIST_IMAGE, 2, st));
+    if (have_ex) RUN(stage_inputs(S, inputs + (size_t)IN_EX_IMG * n, n, IN_EX_IMG, 5, st));
+    for (int k = 0; k < nk; ++k) {
+      const bool on = k <= IN_KP || (k <= IN_GENDER ? have_gt : k <= IN_HIST_KP ? have_hist : have_ex);
+      C.in[k] = on ? S.in_stage[k] : nullptr;
+    }
+    rc = frame_step(S, C, record_slot, loss_slot, extra, st, aux, side);
   }
-  DybRep R{};
-  RUN(make_scope(S, act, na, &R));
-  DybRepScope scope(R);
-  RUN(stage_inputs(S, inputs, n, IN_IMAGE, 5, st));
-  if (have_hist) RUN(stage_inputs(S, inputs + (size_t)IN_HIST_IMAGE * n, n, IN_HIST_IMAGE, 2, st));
-  if (have_ex) RUN(stage_inputs(S, inputs + (size_t)IN_EX_IMG * n, n, IN_EX_IMG, 5, st));
-  FullCtx C{};
-  for (int k = 0; k < IN_COUNT; ++k) C.in[k] = nullptr;
-  C.in[IN_IMAGE] = S.in_stage[IN_IMAGE]; C.in[IN_KP] = S.in_stage[IN_KP];
-  if (have_gt) { C.in[IN_GT_POSE] = S.in_stage[IN_GT_POSE]; C.in[IN_GT_BETAS] = S.in_stage[IN_GT_BETAS]; C.in[IN_GENDER] = S.in_stage[IN_GENDER]; }
-  if (have_hist) { C.in[IN_HIST_IMAGE] = S.in_stage[IN_HIST_IMAGE]; C.in[IN_HIST_KP] = S.in_stage[IN_HIST_KP]; }
-  if (have_ex) for (int k = IN_EX_IMG; k <= IN_EX_POSE3D; ++k) C.in[k] = S.in_stage[k];
-  for (int r = 0; r < n; ++r) extra_steps[r] = 0;
-  return adapt_full_impl(S, C, record_slot, loss_slot, extra_steps, st, aux);
+  if (extra_steps)
+    for (int r = 0; r < n; ++r) extra_steps[r] = extra[r];
+  return rc;
 }
-
+// One sequence, frame-loss set: image [B][3][H][W], kp2d [B][49][3]; gt_pose / gt_betas / gender may be NULL with metrics = 0.
 extern "C" int dyb_stepper_adapt_frame(void* stepper, const float* image, const float* kp2d, const float* gt_pose,
                                        const float* gt_betas, const long long* gender, int record_slot, int loss_slot,
                                        hipStream_t st, hipStream_t aux, hipStream_t side) {
-  Stepper* Sp = reinterpret_cast<Stepper*>(stepper);
-  DYB_REQUIRE(Sp && image && kp2d, DYB_ERR_ARG);
-  RUN(check_ready(*Sp));
-  DYB_REQUIRE(Sp->nrep == 1, DYB_ERR_ARG);
-  return adapt_frame_impl(*Sp, image, kp2d, gt_pose, gt_betas, gender, record_slot, loss_slot, st, aux, side);
+  Stepper* S = reinterpret_cast<Stepper*>(stepper);
+  DYB_REQUIRE(S && image && kp2d && S->nrep == 1, DYB_ERR_ARG);
+  const void* inputs[5] = {image, kp2d, gt_pose, gt_betas, gender};
+  return adapt(*S, inputs, 5, record_slot, loss_slot, nullptr, st, aux, side);
 }
-// The same frame step for `replicas` independent sequences at once: every launch of the chain covers all of them (replica
-// = a grid dimension, dyb_common.h), each with its own weights / Adam moments / workspace / records - theta, adam_m, adam_v
-// are [replicas][param floats], records [replicas][record_capacity][record_floats], loss_log [replicas][loss_capacity]
-// [loss_floats], the workspace `replicas` blobs.  inputs: HOST array of 5 x replicas device pointers, kind-major:
-// image[r], kp2d[r], gt_pose[r], gt_betas[r], gender[r] (the last three may be NULL with metrics = 0).
+// The same for the stepper's replicas: theta, adam_m, adam_v are [replicas][param floats], records [replicas][record_capacity]
+// [record_floats], loss_log [replicas][loss_capacity][loss_floats], the workspace `replicas` blobs.  inputs: 5 x replicas pointers -
+// image[r], kp2d[r], gt_pose[r], gt_betas[r], gender[r].
 extern "C" int dyb_stepper_adapt_frames(void* stepper, const void* const* inputs, int record_slot, int loss_slot, hipStream_t st,
                                         hipStream_t aux, hipStream_t side) {
-  Stepper* Sp = reinterpret_cast<Stepper*>(stepper);
-  DYB_REQUIRE(Sp && inputs, DYB_ERR_ARG);
-  Stepper& S = *Sp;
-  RUN(check_ready(S));
-  const int n = S.nrep;
-  if (n == 1)
-    return adapt_frame_impl(S, (const float*)inputs[0], (const float*)inputs[1], (const float*)inputs[2], (const float*)inputs[3],
-                            (const long long*)inputs[4], record_slot, loss_slot, st, aux, side);
-  int act[DYB_MAX_REPLICAS];
-  const int na = active_set(S, act);
-  // replicas + side stream: the owed final inference of frame f would read staging buffers the next call has already refilled,
-  // under the next frame's launch scope - replica groups run their tail in line
-  DYB_REQUIRE(!(S.use_side && side && side != st), DYB_ERR_UNSUPPORTED);
-  DybRep R{};
-  RUN(make_scope(S, act, na, &R));
-  DybRepScope scope(R);
-  for (int i = 0; i < na; ++i) DYB_REQUIRE(inputs[0 * n + act[i]] && inputs[1 * n + act[i]], DYB_ERR_ARG);
-  // previous frame's tail on the side stream still reads the staged inputs
-  hipStream_t gst = st;
-  RUN(side_wait(S));
-  if (S.side_pending) HIPOK(hipStreamWaitEvent(gst, S.e_side, 0));
-  RUN(stage_inputs(S, inputs, n, IN_IMAGE, 5, gst));
-  const bool have_gt = inputs[2 * n + act[0]] && inputs[3 * n + act[0]] && inputs[4 * n + act[0]];
-  if (S.use_side && side && side != st) {
-    // the ground-truth meshes are issued on the side stream: it has to see the staged inputs
-    HIPOK(hipEventRecord(S.e_gt, st));
-    HIPOK(hipStreamWaitEvent(side, S.e_gt, 0));
-  }
-  return adapt_frame_impl(S, S.in_stage[0], S.in_stage[1], have_gt ? S.in_stage[2] : nullptr, have_gt ? S.in_stage[3] : nullptr,
-                          have_gt ? reinterpret_cast<const long long*>(S.in_stage[4]) : nullptr, record_slot, loss_slot, st, aux, side);
+  Stepper* S = reinterpret_cast<Stepper*>(stepper);
+  DYB_REQUIRE(S && inputs, DYB_ERR_ARG);
+  return adapt(*S, inputs, 5, record_slot, loss_slot, nullptr, st, aux, side);
+}
+// One sequence, full term set: inputs = 12 pointers (image, kp2d, gt_pose, gt_betas, gender, hist_image, hist_kp, ex_img, ex_kp,
+// ex_pose, ex_betas, ex_pose3d; the history pair NULL while there is no frame `interval` steps back, the exemplar five NULL when a
+// retrieval callback is set).  *extra_steps receives the number of dynamic-loop iterations taken.
+extern "C" int dyb_stepper_adapt_frame_full(void* stepper, const void* const* inputs, int record_slot, int loss_slot, int* extra_steps,
+                                            hipStream_t st, hipStream_t aux) {
+  Stepper* S = reinterpret_cast<Stepper*>(stepper);
+  DYB_REQUIRE(S && inputs && extra_steps, DYB_ERR_ARG);
+  DYB_REQUIRE(S->nrep == 1, DYB_ERR_UNSUPPORTED);
+  return adapt(*S, inputs, IN_COUNT, record_slot, loss_slot, extra_steps, st, aux, nullptr);
+}
+// The same for the stepper's replicas, teacher / history / exemplar passes included: 12 x replicas pointers; the history pair must be
+// present for all active replicas or for none; the exemplar five may be NULL when a per-replica retrieval callback
+// ("retrieve_rep_fn") is set.  teacher is [replicas][param floats], gate_log [replicas][...], gate_host 16 floats per replica,
+// feat5_out [replicas][B][2048].  extra_steps: `replicas` ints.
+extern "C" int dyb_stepper_adapt_frames_full(void* stepper, const void* const* inputs, int record_slot, int loss_slot, int* extra_steps,
+                                             hipStream_t st, hipStream_t aux) {
+  Stepper* S = reinterpret_cast<Stepper*>(stepper);
+  DYB_REQUIRE(S && inputs && extra_steps, DYB_ERR_ARG);
+  return adapt(*S, inputs, IN_COUNT, record_slot, loss_slot, extra_steps, st, aux, nullptr);
 }
 // make `st` wait for everything the stepper has in flight on its side stream (before reading records / the final prediction)
 extern "C" int dyb_stepper_join(void* stepper, hipStream_t st) {
   Stepper* S = reinterpret_cast<Stepper*>(stepper);
   DYB_REQUIRE(S, DYB_ERR_ARG);
-  RUN(side_wait(*S));
   if ((S->tail.on || S->gtjob.on) && S->tail_stream) RUN(issue_side_work(*S, S->tail_stream));      // the last frame's final inference
   // (every frame step ends with a forward that consumed them; only a step that failed after its backward leaves deferred weight gradients behind)
   if (S->defer_pending && !S->gates_pending) RUN(settle_update(*S, st));

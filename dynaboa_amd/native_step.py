@@ -118,11 +118,6 @@ class NativeStepper:
                 sf("drop_p", float(getattr(adaptor.teacher, "dropout_p", 0.5)))
         self.use_side = 1 if (S == 1 and getattr(adaptor, "_side", None) is not None) else 0
         si("use_side", self.use_side)
-        # DYB_SIDE_THREAD=1: the side stream's launches (previous frame's final forward + record, ground-truth meshes) from a helper thread of
-        # the library (csrc/adapt_step.hip "side_thread").  Off by default: measured on MI355X it changes nothing (93.7 frames/s either way,
-        # host issue 10.41 ms per frame both: the one-sequence frame is bound by the device's chain of ~950 dependent kernels, the
-        # calling thread merely keeps up with it - profiles/r04_sessions.txt, closing session)
-        si("side_thread", 1 if (self.use_side and hmr.theta.is_cuda and os.environ.get("DYB_SIDE_THREAD", "0") == "1") else 0)
         for k in ("lr", "beta1", "beta2", "fastlr", "s2dloss_weight", "shape_prior_weight", "pose_prior_weight"):
             sf(k, getattr(o, k))
         sf("eps", adaptor.optimizer.param_groups[0]["eps"])
@@ -275,63 +270,69 @@ class NativeStepper:
             raise RuntimeError("dyb_stepper_output: pointer outside the workspace")
         return self.ws[off:off + 4 * n].view(torch.float32).view(shape)
 
-    def adapt_frames(self, batches, side_stream=None):
-        """One frame per replica (`batches`: list of S batch dicts).  -> (frame index, first record slot)."""
-        f = self.frame
+    def _step(self, rows, full: bool, side=None):
+        """One frame step: rows[r] = replica r's input tensors in the stepper's kind order (5 kinds, or 12 with the full term set; None =
+        absent), packed kind-major - ptrs[kind * S + r] - for dyb_stepper_adapt_frames / _frames_full.
+        -> (frame index, first record slot, [extra dynamic-loop steps per replica])."""
+        f, S, nk = self.frame, self.S, 12 if full else 5
         if f >= self.loss_log.shape[1]:
             raise RuntimeError("native stepper: more frames than reset_records() announced")
-        if len(batches) != self.S:
-            raise ValueError(f"{self.S} replicas, {len(batches)} batches")
-        cols = [[], [], [], [], []]
-        for b in batches:
-            for k, (key, conv) in enumerate((("image", torch.Tensor.float), ("smpl_j2d", torch.Tensor.float), ("pose", torch.Tensor.float),
-                                             ("betas", torch.Tensor.float), ("gender", torch.Tensor.long))):
-                cols[k].append(conv(b[key].contiguous()))
-        keep = [t for c in cols for t in c]
-        if side_stream is not None and self.use_side:
-            for t in keep:
-                if t.is_cuda:
-                    t.record_stream(side_stream)
+        ptrs = (ctypes.c_void_p * (nk * S))()
+        for r, row in rows.items():
+            for k, t in enumerate(row):
+                ptrs[k * S + r] = None if t is None else t.data_ptr()
+        extra = (ctypes.c_int * S)()
         slot0 = f * self.slots_per_frame
-        side = side_stream.cuda_stream if (side_stream is not None and self.use_side) else None
-        ptrs = (ctypes.c_void_p * (5 * self.S))(*[t.data_ptr() for t in keep])
-        check(self.lib.dyb_stepper_adapt_frames(self.h, ctypes.cast(ptrs, ctypes.c_void_p), slot0, f, stream_of(self.theta),
-                                                self._aux.cuda_stream if self._aux is not None else None, side),
-              "dyb_stepper_adapt_frames")
+        st, aux = stream_of(self.theta), self._aux.cuda_stream if self._aux is not None else None
+        if full:
+            self._cb_error = None
+            self._drop_begin()
+            rc = self.lib.dyb_stepper_adapt_frames_full(self.h, ctypes.cast(ptrs, ctypes.c_void_p), slot0, f, ctypes.cast(extra, ctypes.c_void_p),
+                                                        st, aux)
+            if getattr(self, "_cb_error", None) is not None:
+                raise self._cb_error
+            self._drop_end()
+        else:
+            rc = self.lib.dyb_stepper_adapt_frames(self.h, ctypes.cast(ptrs, ctypes.c_void_p), slot0, f, st, aux, side)
+        check(rc, "dyb_stepper_adapt_frames_full" if full else "dyb_stepper_adapt_frames")
         self._sync_adam_steps()
         # with a side stream the final inference of this frame is issued by the NEXT call (or join()): its inputs stay alive
-        self._prev_keep, self._keep_inputs = getattr(self, "_keep_inputs", None), keep
+        self._prev_keep, self._keep_inputs = getattr(self, "_keep_inputs", None), rows
         self.frame += 1
-        return f, slot0
+        return f, slot0, [int(x) for x in extra]
+
+    def adapt_frames(self, batches, side_stream=None):
+        """One frame per replica (`batches`: list of S batch dicts).  -> (frame index, first record slot)."""
+        if len(batches) != self.S:
+            raise ValueError(f"{self.S} replicas, {len(batches)} batches")
+        rows = {r: [b["image"].contiguous().float(), b["smpl_j2d"].contiguous().float(), b["pose"].contiguous().float(),
+                    b["betas"].contiguous().float(), b["gender"].contiguous().long()] for r, b in enumerate(batches)}
+        side = None
+        if side_stream is not None and self.use_side:
+            side = side_stream.cuda_stream
+            for row in rows.values():
+                for t in row:
+                    if t.is_cuda:
+                        t.record_stream(side_stream)
+        return self._step(rows, False, side)[:2]
 
     def adapt_frame(self, batch: Dict[str, torch.Tensor], side_stream=None):
         return self.adapt_frames([batch], side_stream)
+
+    @staticmethod
+    def _full_row(batch, hist, exemplars):
+        c = lambda t: t if (t.dtype is torch.float32 and t.is_contiguous()) else t.contiguous().float()      # (no new view objects on the common path)
+        row = [c(batch["image"]), c(batch["smpl_j2d"]), c(batch["pose"]), c(batch["betas"]), batch["gender"].contiguous().long()]
+        row += [c(hist[0]), c(hist[1])] if hist is not None else [None, None]
+        row += [c(exemplars[k]) for k in ("img", "keypoints", "pose", "betas", "pose_3d")] if exemplars is not None else [None] * 5
+        return row
 
     def adapt_frame_full(self, batch, hist=None, exemplars=None):
         """One frame of the full term set.  hist = (image, kp2d) of the frame `interval` steps back or None; exemplars = dict
         (img, keypoints, pose, betas, pose_3d) or None when the retrieval callback supplies them.
         -> (frame index, first record slot, extra dynamic-loop steps)."""
-        f = self.frame
-        if f >= self.loss_log.shape[1]:
-            raise RuntimeError("native stepper: more frames than reset_records() announced")
-        c = lambda t: t if (t.dtype is torch.float32 and t.is_contiguous()) else t.contiguous().float()      # (no new view objects on the common path)
-        keep = [c(batch["image"]), c(batch["smpl_j2d"]), c(batch["pose"]), c(batch["betas"]), batch["gender"].contiguous().long()]
-        keep += [c(hist[0]), c(hist[1])] if hist is not None else [None, None]
-        keep += [c(exemplars[k]) for k in ("img", "keypoints", "pose", "betas", "pose_3d")] if exemplars is not None else [None] * 5
-        ptrs = (ctypes.c_void_p * 12)(*[None if t is None else t.data_ptr() for t in keep])
-        extra = ctypes.c_int(0)
-        slot0 = f * self.slots_per_frame
-        self._cb_error = None
-        self._drop_begin()
-        rc = self.lib.dyb_stepper_adapt_frame_full(self.h, ctypes.cast(ptrs, ctypes.c_void_p), slot0, f, ctypes.cast(ctypes.pointer(extra), ctypes.c_void_p),
-                                                   stream_of(self.theta), self._aux.cuda_stream if self._aux is not None else None)
-        if getattr(self, "_cb_error", None) is not None:
-            raise self._cb_error
-        self._drop_end()
-        check(rc, "dyb_stepper_adapt_frame_full")
-        self._sync_adam_steps()
-        self.frame += 1
-        return f, slot0, int(extra.value)
+        f, slot0, extra = self._step({0: self._full_row(batch, hist, exemplars)}, True)
+        return f, slot0, extra[0]
 
     def _drop_begin(self):
         """train-mode teacher: hand the stepper this frame's dropout keys - torch's seed and the NEXT value of the process-wide
@@ -367,35 +368,7 @@ class NativeStepper:
         """One frame of the full term set per ACTIVE replica, in lockstep (lists of length S; entries of inactive replicas None).
         hists[r] = (image, kp2d) or None (all active replicas alike); exemplars[r] = dict or None (retrieval callback).
         -> (frame index, first record slot, [extra dynamic-loop steps per replica])."""
-        f = self.frame
-        if f >= self.loss_log.shape[1]:
-            raise RuntimeError("native stepper: more frames than reset_records() announced")
-        S = self.S
-        c = lambda t: t if (t.dtype is torch.float32 and t.is_contiguous()) else t.contiguous().float()      # (no new view objects on the common path)
-        ptrs = (ctypes.c_void_p * (12 * S))()
-        keep = []
-        for r in getattr(self, "active", range(S)):
-            b = batches[r]
-            row = [c(b["image"]), c(b["smpl_j2d"]), c(b["pose"]), c(b["betas"]), b["gender"].contiguous().long()]
-            row += [c(hists[r][0]), c(hists[r][1])] if hists[r] is not None else [None, None]
-            row += [c(exemplars[r][k]) for k in ("img", "keypoints", "pose", "betas", "pose_3d")] if exemplars[r] is not None else [None] * 5
-            keep.append(row)
-            for k, t in enumerate(row):
-                ptrs[k * S + r] = None if t is None else t.data_ptr()
-        extra = (ctypes.c_int * S)()
-        slot0 = f * self.slots_per_frame
-        self._cb_error = None
-        self._drop_begin()
-        rc = self.lib.dyb_stepper_adapt_frames_full(self.h, ctypes.cast(ptrs, ctypes.c_void_p), slot0, f, ctypes.cast(extra, ctypes.c_void_p),
-                                                    stream_of(self.theta), self._aux.cuda_stream if self._aux is not None else None)
-        if getattr(self, "_cb_error", None) is not None:
-            raise self._cb_error
-        self._drop_end()
-        check(rc, "dyb_stepper_adapt_frames_full")
-        self._sync_adam_steps()
-        self._keep_inputs = keep
-        self.frame += 1
-        return f, slot0, [int(x) for x in extra]
+        return self._step({r: self._full_row(batches[r], hists[r], exemplars[r]) for r in getattr(self, "active", range(self.S))}, True)
 
     def level_row(self, frame: int, row: int, r: int = 0):
         """16-float log row `row` of `frame` (full mode): frame {s2d, shape, pose, total} | teacher {s2d, s3d, shape, pose, loss} |

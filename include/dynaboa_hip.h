@@ -474,15 +474,15 @@ int dyb_render_meshes(const float* verts, const int* faces, const int* adj_ptr, 
  * ~2.5 us of host time per launch instead of ~5.  A stepper owns no memory: theta / Adam moments / tables are the
  * caller's (dyb_stepper_set_p), scratch is one blob (dyb_stepper_workspace_bytes -> dyb_stepper_bind_workspace).
  * Steppers are independent: several may run on different streams from different host threads (sequence replicas
- * sharing one GPU).  Keys:
- *   set_i: n_iter, inner_step, eval_lower (metric record after every inner step), use_side, metrics, adam_step,
- *          record_capacity, loss_capacity, replicas
- *   set_f: lr, beta1, beta2, eps, fastlr, s2dloss_weight, shape_prior_weight, pose_prior_weight
- *   set_p: theta, adam_m, adam_v, init_state [B][160], gmm_means, gmm_precisions, gmm_log_weights, j_regressor_h36m
- *          [17][6890], j14 (device int32[14]), records, loss_log, smpl_{neutral,male,female}_{0..6} and
- *          smpli_{...}_{0..2} (the table order of dyb_lbs_fwd)
- *   get_i: adam_step, record_floats (floats per metric record: pred14 [B][14][3] | gt14 [B][14][3] | mpjpe [B] | pve),
- *          loss_floats (floats per frame in loss_log: (inner_step + 1) x {s2d, shape prior, pose prior, weighted total})
+ * sharing one GPU).  Keys: csrc/dyb_stepper_options.h lists every option once - key, type (set_i / set_f / set_p), environment
+ * variable, whether it is locked once the workspace is bound ("replicas", "fuse_fast", "full": DYB_ERR_ARG afterwards), meaning;
+ * get_i / get_f return any int / double option by its key.  With code of their own:
+ *   set_i: adam_step, adam_step_<replica>, replicas (1..64), logs_bytes, drop_seed, drop_offset
+ *   set_p: smpl_{neutral,male,female}_{0..6} and smpli_{...}_{0..2} (the table order of dyb_lbs_fwd)
+ *   get_i: adam_step, adam_step_<replica>, drop_used, slots_per_frame, record_floats (floats per metric record: pred14 [B][14][3] |
+ *          gt14 [B][14][3] | mpjpe [B] | pve), loss_floats (floats per frame in loss_log: (inner_step + 1) x {s2d, shape prior, pose
+ *          prior, weighted total}; full term set: 16 per level, + optim_steps levels with the dynamic loop)
+ * Unknown keys are errors.
  * dyb_stepper_adapt_frame: gender is int64 [B]; gt_* / gender may be NULL with metrics = 0.  Records go to slots
  * record_slot.. (one per inner step when eval_lower, then the final one).  `aux`: weight-gradient stream (may be NULL);
  * `side`: stream for the final no-grad forward + its metrics (may be NULL), overlapped with the next frame.

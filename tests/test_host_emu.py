@@ -258,40 +258,88 @@ def test_native_stepper_is_bit_identical_to_autograd_path(emu_lib):
     assert abs(a[6]["ul/total"] - g["upper_loss"][0]) < 1e-4 * abs(g["upper_loss"][0])
 
 
-@pytest.mark.skipif(not os.environ.get("DYB_EMU_FULL"), reason="~3 min under the emulator; set DYB_EMU_FULL=1")
-def test_native_stepper_side_stream_work_from_the_helper_thread(emu_lib, monkeypatch):
-    """"side_thread": the side stream's launches (previous frame's final forward + record, this frame's ground-truth meshes) issued by the
-    library's helper thread while the calling thread goes on with the chain.  The emulator executes a launch where it is issued, so the
-    two threads really interleave here: weights, Adam state and every metric record must equal the in-line run bit for bit - i.e. the
-    calling thread waits for the helper before it touches anything the helper writes."""
-    from types import SimpleNamespace
-    from dynaboa_amd import assets, benchmark as DB, native_step as NS
-    from dynaboa_amd._abi import check
-    from dynaboa_amd.base_adaptor import synthetic_bundle
-    frames = [assets.make_frame(s, 1, seed=22) for s in range(3)]
-    orig = NS.NativeStepper.adapt_frames
-    outs = []
-    for helper in (0, 1):
-        def wrapped(self, batches, side_stream=None, helper=helper):
-            self.use_side = 1
-            check(self.lib.dyb_stepper_set_i(self.h, b"use_side", 1), "use_side")
-            check(self.lib.dyb_stepper_set_i(self.h, b"side_thread", helper), "side_thread")
-            return orig(self, batches, SimpleNamespace(cuda_stream=2))       # any non-null handle is a stream to the emulator
-        monkeypatch.setattr(NS.NativeStepper, "adapt_frames", wrapped)
-        o = DB.frame_only_options(inner_step=1)
-        o.native_step, o.deferred_metrics = 1, 1
-        ad = DB.Adaptor(o, synthetic_bundle(seed=22, identity_pose=True, randomize_norm=True), device="cpu")
-        res = ad.excute(frames, nframes=3)
-        assert ad._native is not None
-        st = ad.optimizer.state[ad.model.module.theta]
-        outs.append((ad.model.module.theta.detach().clone(), st["exp_avg"].clone(), st["exp_avg_sq"].clone(),
-                     np.ravel(np.array(res["pampjpe"], np.float64)), np.ravel(np.array(res["mpjpe"], np.float64)),
-                     np.ravel(np.array(res["pve"], np.float64))))
-    for a, b in zip(outs[0][:3], outs[1][:3]):
-        assert torch.equal(a, b)
-    for a, b in zip(outs[0][3:], outs[1][3:]):
-        assert a.size == 3 and np.isfinite(a).all()                          # one final record per frame
-        np.testing.assert_array_equal(a, b)
+def _stepper_option_rows():
+    """csrc/dyb_stepper_options.h as (member, key, environment variable or None, type I | F | P, locked once bound)."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "dynaboa_amd", "csrc", "dyb_stepper_options.h")).read()
+    rows = [(m[0], m[1], m[2] or None, m[3], m[4] == "1")
+            for m in re.findall(r'^\s*X\((\w+), "(\w+)", (?:nullptr|"(\w+)"), ([IFP]), ([01]), "', text, re.M)]
+    assert text.count("\n  X(") == len(rows)                                    # every row of the list was understood
+    return rows
+
+
+def test_native_stepper_option_table(emu_lib, monkeypatch):
+    """The stepper's options are one list (csrc/dyb_stepper_options.h): every row can be set by its key and - int and double rows - read
+    back by it; a row's environment variable is read when the stepper is created and a later set_i wins; unknown keys (and keys of another
+    type) are errors for all three setters; what sizes the workspace ("replicas", "fuse_fast", "full") can be set until the workspace is
+    bound and is refused afterwards - "full" used to be accepted there and left the full-set buffers of the next frame step unallocated."""
+    from dynaboa_amd.hmr import get_layout
+    lib, L = emu_lib, get_layout(1)
+    rows = _stepper_option_rows()
+    assert {r[3] for r in rows} == {"I", "F", "P"} and len(rows) >= 60
+    envs = [r for r in rows if r[2]]
+    assert {r[2] for r in envs} >= {"DYB_UPD_OVERLAP", "DYB_UPD_LATE", "DYB_WGRAD_DEFER", "DYB_FUSE_FAST", "DYB_FUSE_ADAM", "DYB_FUSE_EMA",
+                                    "DYB_PAR_PASSES", "DYB_PAR_MAX_REPLICAS", "DYB_SHARE_DYN_FWD"}
+    assert all(r[3] == "I" for r in envs)
+
+    def create():
+        h = ctypes.c_void_p()
+        assert lib.dyb_stepper_create(L.plan, 1, 224, 224, ctypes.byref(h)) == 0 and h
+        return h
+    h = create()
+    try:
+        dummy = torch.zeros(16)
+        for i, (_member, key, _env, typ, _locked) in enumerate(rows):
+            k = key.encode()
+            if typ == "I":
+                for v in (3 + i, 1):
+                    assert lib.dyb_stepper_set_i(h, k, v) == 0, key
+                    assert lib.dyb_stepper_get_i(h, k) == v, key
+                assert lib.dyb_stepper_set_f(h, k, 0.5) != 0 and lib.dyb_stepper_set_p(h, k, dummy.data_ptr()) != 0, key
+            elif typ == "F":
+                for v in (0.25 + i / 1024.0, 0.5):                           # (inside the range "drop_p" accepts)
+                    assert lib.dyb_stepper_set_f(h, k, v) == 0, key
+                    assert lib.dyb_stepper_get_f(h, k) == v, key
+                assert lib.dyb_stepper_set_i(h, k, 1) != 0 and lib.dyb_stepper_set_p(h, k, dummy.data_ptr()) != 0, key
+            else:
+                assert lib.dyb_stepper_set_p(h, k, dummy.data_ptr()) == 0, key
+                assert lib.dyb_stepper_set_i(h, k, 1) != 0 and lib.dyb_stepper_set_f(h, k, 0.5) != 0, key
+        assert lib.dyb_stepper_set_f(h, b"drop_p", 1.0) != 0 and lib.dyb_stepper_get_f(h, b"drop_p") == 0.5
+        assert lib.dyb_stepper_set_i(h, b"no_such_option", 1) != 0
+        assert lib.dyb_stepper_set_f(h, b"no_such_option", 1.0) != 0
+        assert lib.dyb_stepper_set_p(h, b"no_such_option", dummy.data_ptr()) != 0
+        assert lib.dyb_stepper_get_i(h, b"no_such_option") == -1 and lib.dyb_stepper_get_f(h, b"no_such_option") == -1.0
+    finally:
+        lib.dyb_stepper_destroy(h)
+    # the environment is read at create; a later set_i wins
+    for i, r in enumerate(envs):
+        monkeypatch.setenv(r[2], str(5 + i))
+    h = create()
+    try:
+        for i, r in enumerate(envs):
+            assert lib.dyb_stepper_get_i(h, r[1].encode()) == 5 + i, r
+            assert lib.dyb_stepper_set_i(h, r[1].encode(), 2) == 0 and lib.dyb_stepper_get_i(h, r[1].encode()) == 2, r
+    finally:
+        lib.dyb_stepper_destroy(h)
+    for r in envs:
+        monkeypatch.delenv(r[2])
+    # what the workspace's layout depends on is locked once the workspace is bound
+    locked = {r[1] for r in rows if r[4]}
+    assert locked == {"fuse_fast", "full"}
+    h = create()
+    try:
+        for key, v in (("replicas", 2), ("fuse_fast", 1), ("full", 1), ("replicas", 1), ("fuse_fast", 0), ("full", 0)):
+            assert lib.dyb_stepper_set_i(h, key.encode(), v) == 0, key
+        nbytes = int(lib.dyb_stepper_workspace_bytes(h))
+        ws = torch.empty(nbytes, dtype=torch.uint8)
+        assert lib.dyb_stepper_bind_workspace(h, ws.data_ptr(), nbytes, None) == 0
+        for key in ("replicas", "fuse_fast", "full"):
+            assert lib.dyb_stepper_set_i(h, key.encode(), 1) != 0, key
+        assert lib.dyb_stepper_get_i(h, b"full") == 0 and lib.dyb_stepper_get_i(h, b"fuse_fast") == 0
+        assert lib.dyb_stepper_set_i(h, b"inner_step", 2) == 0                # (everything else stays settable)
+    finally:
+        lib.dyb_stepper_destroy(h)
 
 
 @pytest.mark.skipif(not os.environ.get("DYB_EMU_FULL"), reason="~4 min under the emulator; set DYB_EMU_FULL=1")
