@@ -236,6 +236,17 @@ def make_frame(step: int, batch_size: int = 1, seed: int = 22) -> Dict[str, torc
     return dict(image=image, smpl_j2d=kp, pose=pose, betas=betas, gender=gender)
 
 
+def make_online_frame(step: int, seed: int = 22) -> Dict[str, torch.Tensor]:
+    """One frame of the online path (reference dynaboa_webcam.py ``dataprocess``'s outputs): the normalised crop and the keypoint
+    array with the 25 OpenPose BODY_25 detections in slots 0..24 - roughly 80 % of them confident -, slots 25..48 zero."""
+    g = torch.Generator().manual_seed(seed * 1_000_003 + 500_009 + step)
+    image = torch.randn(1, 3, C.IMG_RES, C.IMG_RES, generator=g)
+    kp = torch.zeros(1, C.NUM_OUT_JOINTS, 3)
+    kp[:, :25, :2] = torch.rand(1, 25, 2, generator=g) * 2 - 1
+    kp[:, :25, 2] = (torch.rand(1, 25, generator=g) < 0.8).float()
+    return dict(image=image, smpl_j2d=kp)
+
+
 _EX_DEVICE_CACHE: Dict[tuple, Dict[str, torch.Tensor]] = {}
 EX_DEVICE_CACHE_STEPS = 2          # steps kept per (sample_num, device, seed): the current one and its predecessor
 

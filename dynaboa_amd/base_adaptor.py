@@ -29,7 +29,7 @@ from . import assets as A
 from . import constants
 from .hmr import hmr
 from .fused_level import clear_last_forward, level_forward
-from .losses import (AUX_MAX_BATCH, MaxMixturePrior, frame_losses, labelled_term, motion_term, pose_prior, projection_normed,
+from .losses import (AUX_MAX_BATCH, KP_WINDOWS, MaxMixturePrior, frame_losses, kp_set_refusal, labelled_term, motion_term, pose_prior, projection_normed,
                      teacher_term)
 from .maml import MAML
 from .optim import Adam, ema_update
@@ -212,6 +212,10 @@ class BaseAdaptor:
         stale = self.global_step - self.options.interval - 1
         self.history.pop(stale, None)            # the reference never prunes (602 KB/frame host growth)
 
+    def motion_on(self) -> bool:
+        """The motion term's gate: a frame `interval` steps back exists (global_step counts from 1 here: save_hist came first)."""
+        return bool(self.options.use_motion and (self.global_step - self.options.interval) > 0)
+
     def get_hist(self):
         h = self.history[self.global_step - self.options.interval]
         return h["image"], h["s2d"]
@@ -259,9 +263,10 @@ class BaseAdaptor:
         h_rot, h_shape, h_cam = model(hist_image)
         h_s3d = self.decode_smpl_params(h_rot, h_shape)["s3d"]
         h_s2d = self.projection(h_cam, h_s3d)["normed"]
-        pred_motion = pred_s2d - h_s2d[:, 25:]
-        gt_motion = gt_s2d[:, :, :-1] - hist_s2d[:, 25:, :-1]
-        conf = ((hist_s2d[:, 25:, -1:] + gt_s2d[:, :, -1:]) == 2).float()
+        lo, n = KP_WINDOWS[getattr(self.options, "kp_set", "gt24")]          # (pred_s2d / gt_s2d arrive cut to the same window)
+        pred_motion = pred_s2d - h_s2d[:, lo:lo + n]
+        gt_motion = gt_s2d[:, :, :-1] - hist_s2d[:, lo:lo + n, :-1]
+        conf = ((hist_s2d[:, lo:lo + n, -1:] + gt_s2d[:, :, -1:]) == 2).float()
         loss = (((pred_motion - gt_motion) ** 2) * conf).mean()
         self.fit_losses[f"{prefix}/motion_loss"] = loss
         return loss
@@ -282,7 +287,7 @@ class BaseAdaptor:
         hist_image, hist_s2d = self.get_hist()
         h_rot, h_shape, h_cam = model(hist_image)
         h_s3d = self.decode_smpl_params(h_rot, h_shape)["s3d"]
-        loss, _ = motion_term(rot, shape, cam, s3d, h_cam, h_s3d, gt_keypoints_2d, hist_s2d)
+        loss, _ = motion_term(rot, shape, cam, s3d, h_cam, h_s3d, gt_keypoints_2d, hist_s2d, kp_set=getattr(self.options, "kp_set", "gt24"))
         self.fit_losses[f"{prefix}/motion_loss"] = loss
         return loss
 
@@ -312,6 +317,11 @@ class BaseAdaptor:
     def _level(self, level, image, gt_keypoints_2d, h36m_batch, learner):
         o = self.options
         tag = "ll" if level == "lower" else "ul"
+        kp_set = getattr(o, "kp_set", "gt24")
+        why = kp_set_refusal(o)
+        if why:
+            raise ValueError(why)
+        kp_lo, kp_n = KP_WINDOWS[kp_set]
         quiet = getattr(self, "_replay", None) is not None     # a second-order re-evaluation: no logging, same exemplars
         loss = None
         s2d = None
@@ -322,7 +332,7 @@ class BaseAdaptor:
             # three-module composition below, which stays for use_frame_losses_* = 0 and as the cross-check
             loss, comps, rot, shape, cam, s3d, _vts, feats = level_forward(
                 learner, self.smpl_neutral, self.gmm_f, image, gt_keypoints_2d, o.s2dloss_weight, o.shape_prior_weight,
-                o.pose_prior_weight)
+                o.pose_prior_weight, kp_set=kp_set)
         else:
             clear_last_forward()                 # (a remembered fused forward must not be mistaken for this level's: ADVICE r3)
             rot, shape, cam, feats = learner(image, need_feature=True)
@@ -333,7 +343,7 @@ class BaseAdaptor:
         if getattr(o, f"use_frame_losses_{level}"):
             if not fused:
                 loss, comps = frame_losses(rot, shape, cam, s3d, gt_keypoints_2d, self.gmm_f, o.s2dloss_weight,
-                                           o.shape_prior_weight, o.pose_prior_weight)
+                                           o.shape_prior_weight, o.pose_prior_weight, kp_set=kp_set)
             if not quiet:
                 if level == "lower":
                     self.kp2dlosses_lower.append(comps[0])
@@ -353,9 +363,9 @@ class BaseAdaptor:
                     t = (self._teacher_term(image, rot, shape, cam, s3d) if kern else self.cal_teacher_loss(image, rot, shape, s2d, s3d))
                     t = t * o.teacherloss_weight
                     loss = t if loss is None else loss + t
-                if o.use_motion and (self.global_step - o.interval) > 0:
+                if self.motion_on():
                     m = (self._motion_term(learner, rot, shape, cam, s3d, gt_keypoints_2d, prefix="ul") if kern else
-                         self.cal_motion_loss(learner, s2d[:, 25:], gt_keypoints_2d[:, 25:], prefix="ul"))
+                         self.cal_motion_loss(learner, s2d[:, kp_lo:kp_lo + kp_n], gt_keypoints_2d[:, kp_lo:kp_lo + kp_n], prefix="ul"))
                     loss = loss + m * o.motionloss_weight
             if o.retrieval:
                 h36m_batch = self._replay["h36m"] if quiet else self.retrieval(feats[5])

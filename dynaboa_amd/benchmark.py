@@ -292,7 +292,7 @@ class Adaptor(BaseAdaptor):
         synthetic bundle; None = the stepper's retrieval callback asks self.retrieval per level)."""
         o = self.options
         hist = None
-        if o.use_motion and (self.global_step - o.interval) > 0 and (o.use_temporal_losses_upper or o.use_temporal_losses_lower):
+        if self.motion_on() and (o.use_temporal_losses_upper or o.use_temporal_losses_lower):
             hist = self.get_hist()
         ex = None
         if (o.lower_level_mixtrain or o.upper_level_mixtrain) and self.bundle is not None:

@@ -42,9 +42,9 @@ int dyb_lbs_bwd(const float* const*, const int* const*, const float*, const floa
                 int, void*, size_t, hipStream_t);
 int dyb_regress_joints(const float*, const float*, float*, int, int, hipStream_t);
 int dyb_rodrigues_fwd(const float*, float*, int, hipStream_t);
-int dyb_frame_losses(const float*, const float*, int, const float*, int, const float*, const float*, const float*, const float*,
-                     const float*, float, float, float, float*, float*, float*, int, float*, int, float*, int, void*, size_t,
-                     hipStream_t);
+int dyb_frame_losses_kp(const float*, const float*, int, const float*, int, const float*, const float*, const float*, const float*,
+                        const float*, float, float, float, float*, float*, float*, int, float*, int, float*, int, int, void*, size_t,
+                        hipStream_t);
 int dyb_scale_add(const float*, const float*, const float*, float*, size_t, hipStream_t);
 int dyb_head_grad_combine(const float*, const float*, const float*, const float*, const float*, const float*, const float*,
                           const float*, const float*, float*, float*, int, hipStream_t);
@@ -52,9 +52,9 @@ int dyb_fastweight_update(const float*, const float*, float*, float, size_t, hip
 int dyb_adam_step(float*, const float*, float*, float*, float, float, float, float, float, size_t, hipStream_t);
 int dyb_ema_update(float*, const float*, float, size_t, hipStream_t);
 int dyb_axpby(const float*, float*, float, float, size_t, hipStream_t);
-int dyb_aux_loss_terms(int, int, int, float, const float*, const float*, int, const float*, int, const float*, const float*,
-                       const float*, int, const float*, int, const float*, const float*, const float*, const float*, const float*,
-                       const float*, float*, float*, float*, float*, float*, float*, float*, hipStream_t);
+int dyb_aux_loss_terms_kp(int, int, int, float, const float*, const float*, int, const float*, int, const float*, const float*,
+                          const float*, int, const float*, int, const float*, const float*, const float*, const float*, const float*,
+                          const float*, float*, float*, float*, float*, float*, float*, float*, int, hipStream_t);
 int dyb_hmr_feature_info(const void*, int, long long*, int*, int*);
 }
 int dyb_adam_step_rep(float*, const float*, float*, float*, float, float, const float*, const float*, float, size_t, hipStream_t);   // optim.hip
@@ -237,6 +237,7 @@ struct Stepper {
   // the full loss set (reference defaults): teacher / motion / labelled-exemplar terms, dynamic-BOA gate
   int full = 0, temporal_lower = 0, temporal_upper = 1, use_teacher = 1, use_motion = 1, interval = 5, mix_lower = 1, mix_upper = 1,
       dynamic = 1, optim_steps = 7;
+  int kp_set = 0;                     // keypoint window of the frame head's 2-D term and of the motion term: 0 gt24 | 1 op25 (losses.hip)
   double teacher_w = 0.1, motion_w = 0.8, label_w = 0.1, alpha = 0.1, cos_thr = 3.1e-4;
   float* teacher = nullptr;           // teacher parameter arena (caller's)
   // train-mode teacher (the reference never calls teacher.eval(): base_adaptor.py:151-158 - its teacher forwards run with live
@@ -528,7 +529,9 @@ extern "C" int dyb_stepper_set_i(void* stepper, const char* key, long long v) {
     const int r = atoi(k.c_str() + 10);
     DYB_REQUIRE(r >= 0 && r < DYB_MAX_REPLICAS, DYB_ERR_ARG);
     S->adam_t_rep[r] = v;
-    if (v > S->adam_t) S->adam_t = v;
+    S->adam_t = 0;                                    // "adam_step" reports the largest count among the handle's replicas
+    for (int q = 0; q < S->nrep || q <= r; ++q)
+      if (S->adam_t_rep[q] > S->adam_t) S->adam_t = S->adam_t_rep[q];
   }
   else if (k == "drop_seed") S->drop_seed = (unsigned long long)v;
   else if (k == "drop_offset") { S->drop_off = (unsigned long long)v; S->drop_used = 0; }
@@ -673,6 +676,7 @@ static int check_ready(const Stepper& S) {
     }
   }
   DYB_REQUIRE(S.inner_step >= 0 && S.inner_step <= 16 && S.n_iter >= 1 && S.n_iter <= 3, DYB_ERR_UNSUPPORTED);
+  DYB_REQUIRE(S.kp_set == 0 || S.kp_set == 1, DYB_ERR_ARG);       // (the setter stores any value: refused here, before the first launch)
   return DYB_OK;
 }
 
@@ -702,9 +706,9 @@ static int pass_forward(Stepper& S, Pass& P, const float* theta, const float* im
 static int pass_frame_head(Stepper& S, Pass& P, const float* kp2d, hipStream_t st) {
   const float* rot = P.acts + S.off_rot;
   const float* state = P.acts + S.off_state;
-  return dyb_frame_losses(rot, state + 144, STATE_LD, state + 154, STATE_LD, P.joints, kp2d, S.gmm_means, S.gmm_prec, S.gmm_logw,
-                          (float)S.w2d, (float)S.wshape, (float)S.wpose, P.losses, P.drot_l, P.dshape_l, 10, P.dcam_l, 3, P.djoints_l,
-                          S.B, P.lws, (size_t)S.B * 16, st);
+  return dyb_frame_losses_kp(rot, state + 144, STATE_LD, state + 154, STATE_LD, P.joints, kp2d, S.gmm_means, S.gmm_prec, S.gmm_logw,
+                             (float)S.w2d, (float)S.wshape, (float)S.wpose, P.losses, P.drot_l, P.dshape_l, 10, P.dcam_l, 3, P.djoints_l,
+                             S.B, S.kp_set, P.lws, (size_t)S.B * 16, st);
 }
 // where a weight update goes by arena ranges (weight_update) - and a chain backward may defer weight gradients ("wgrad_defer")
 static bool ranged_form(const Stepper& S, hipStream_t st, hipStream_t aux) {
@@ -1053,10 +1057,10 @@ static int level(Stepper& S, LevelCtx& C, Pass& P, const float* cur, float* nxt,
     RUN(pass_forward(S, S.ex, cur, (const float*)C.in[IN_EX_IMG], s, chain));
     RUN(dyb_rodrigues_fwd((const float*)C.in[IN_EX_POSE], S.ex_rot, B * 24, s));          // utils/geometry.py:9-24 on the exemplar pose
     const float* es = S.ex.acts + S.off_state;
-    return dyb_aux_loss_terms(2, B, 0, (float)S.label_w, S.ex.acts + S.off_rot, es + 144, STATE_LD, es + 154, STATE_LD, S.ex.joints, nullptr,
-                              nullptr, 0, nullptr, 0, nullptr, (const float*)C.in[IN_EX_KP], nullptr, S.ex_rot,
-                              (const float*)C.in[IN_EX_BETAS], (const float*)C.in[IN_EX_POSE3D], S.vals_l, S.exg_rot, S.exg_shape, S.exg_cam,
-                              S.exg_joints, nullptr, nullptr, s);
+    return dyb_aux_loss_terms_kp(2, B, 0, (float)S.label_w, S.ex.acts + S.off_rot, es + 144, STATE_LD, es + 154, STATE_LD, S.ex.joints, nullptr,
+                                 nullptr, 0, nullptr, 0, nullptr, (const float*)C.in[IN_EX_KP], nullptr, S.ex_rot,
+                                 (const float*)C.in[IN_EX_BETAS], (const float*)C.in[IN_EX_POSE3D], S.vals_l, S.exg_rot, S.exg_shape, S.exg_cam,
+                                 S.exg_joints, nullptr, nullptr, 0, s);
   };
   if (par && label) {
     DYB_REQUIRE(C.in[IN_EX_IMG] && C.in[IN_EX_KP] && C.in[IN_EX_POSE] && C.in[IN_EX_BETAS] && C.in[IN_EX_POSE3D], DYB_ERR_ARG);
@@ -1081,9 +1085,9 @@ static int level(Stepper& S, LevelCtx& C, Pass& P, const float* cur, float* nxt,
       RUN(pass_forward(S, S.teach, S.teacher, image, st));
     }
     const float* ts = S.teach.acts + S.off_state;
-    RUN(dyb_aux_loss_terms(0, B, 0, (float)S.teacher_w, rot, state + 144, STATE_LD, state + 154, STATE_LD, P.joints,
-                           S.teach.acts + S.off_rot, ts + 144, STATE_LD, ts + 154, STATE_LD, S.teach.joints, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, S.vals_t, S.ext_rot, S.ext_shape, S.ext_cam, S.ext_joints, nullptr, nullptr, st));
+    RUN(dyb_aux_loss_terms_kp(0, B, 0, (float)S.teacher_w, rot, state + 144, STATE_LD, state + 154, STATE_LD, P.joints,
+                              S.teach.acts + S.off_rot, ts + 144, STATE_LD, ts + 154, STATE_LD, S.teach.joints, nullptr, nullptr, nullptr,
+                              nullptr, nullptr, S.vals_t, S.ext_rot, S.ext_shape, S.ext_cam, S.ext_joints, nullptr, nullptr, 0, st));
     ext = true;
   }
   if (motion) {
@@ -1091,9 +1095,9 @@ static int level(Stepper& S, LevelCtx& C, Pass& P, const float* cur, float* nxt,
     if (par) HIPOK(hipStreamWaitEvent(st, S.par_ev[1], 0));
     else RUN(pass_forward(S, S.hist, cur, (const float*)C.in[IN_HIST_IMAGE], st));
     const float* hs = S.hist.acts + S.off_state;
-    RUN(dyb_aux_loss_terms(1, B, ext ? 1 : 0, (float)S.motion_w, rot, state + 144, STATE_LD, state + 154, STATE_LD, P.joints, nullptr,
-                           nullptr, 0, hs + 154, STATE_LD, S.hist.joints, kp, (const float*)C.in[IN_HIST_KP], nullptr, nullptr, nullptr,
-                           S.vals_m, S.ext_rot, S.ext_shape, S.ext_cam, S.ext_joints, S.hg_cam, S.hg_joints, st));
+    RUN(dyb_aux_loss_terms_kp(1, B, ext ? 1 : 0, (float)S.motion_w, rot, state + 144, STATE_LD, state + 154, STATE_LD, P.joints, nullptr,
+                              nullptr, 0, hs + 154, STATE_LD, S.hist.joints, kp, (const float*)C.in[IN_HIST_KP], nullptr, nullptr, nullptr,
+                              S.vals_m, S.ext_rot, S.ext_shape, S.ext_cam, S.ext_joints, S.hg_cam, S.hg_joints, S.kp_set, st));
     ext = true;
     if (par) {
       HIPOK(hipEventRecord(S.par_ev[2], st));

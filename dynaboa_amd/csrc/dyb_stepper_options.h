@@ -31,6 +31,7 @@
   X(mix_upper, "mix_upper", nullptr, I, 0, "labelled-exemplar term on the upper level")                                                       \
   X(dynamic, "dynamic", nullptr, I, 0, "dynamic loop: repeat the upper level while feature 12 still moves")                                   \
   X(optim_steps, "optim_steps", nullptr, I, 0, "its iteration limit")                                                                         \
+  X(kp_set, "kp_set", nullptr, I, 0, "keypoint window of the 2D term and the motion term: 0 gt24 (joints 25..48) | 1 op25 (joints 0..24)")   \
   X(record_capacity, "record_capacity", nullptr, I, 0, "metric-record slots behind `records`")                                                \
   X(loss_capacity, "loss_capacity", nullptr, I, 0, "frames behind `loss_log` / `gate_log`")
 #define DYB_STEPPER_OPTIONS_F(X)                                                                                                              \

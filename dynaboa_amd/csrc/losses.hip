@@ -14,6 +14,7 @@
 
 #define NJ 24
 #define NJ49 49
+#define NKP_MAX 25      // the larger of the two keypoint windows (staging arrays of the 2-D term)
 #define NG 8
 #define ND 69
 #define FOCAL 5000.0f
@@ -427,6 +428,14 @@ extern "C" int dyb_gmm_prior(const float* pose69, const float* gmm_means, const 
 // ------------------------------------------------------------------------------------------
 // fused frame losses, value + gradient
 // ------------------------------------------------------------------------------------------
+// Keypoint sets: the window of the 49-joint convention that the 2-D keypoint term and the motion term supervise.
+//   0 "gt24"  joints 25..48, mean over B * 24 * 2   (ground-truth style joints: reference base_adaptor.py:229,234, :379-398)
+//   1 "op25"  joints  0..24, mean over B * 25 * 2   (OpenPose BODY_25 detections: dynaboa_webcam.py:164-182, :206, :248)
+static inline bool kp_window(int kp_set, int* lo, int* n) {
+  if (kp_set == 0) { *lo = 25; *n = 24; return true; }
+  if (kp_set == 1) { *lo = 0; *n = 25; return true; }
+  return false;
+}
 struct FrameLossArgs {
   const float* rot;      // [B][24][9]
   const float* shape;    // [B][lds]  (10 used)
@@ -442,6 +451,7 @@ struct FrameLossArgs {
   float* dcam;           // [B][lddc]
   float* djoints;        // [B][49][3]
   int lds, ldc, ldds, lddc, B;
+  int kp_lo, kp_n;       // keypoint window: joints kp_lo .. kp_lo + kp_n - 1 (kp_n <= NKP_MAX)
   float w2d, wshape, wpose;
   // tangent form only (S = dualf): tangents of the four inputs and of the four gradients, each shaped like its value array
   const float *trot, *tshape, *tcam, *tjoints;
@@ -462,8 +472,8 @@ __global__ __launch_bounds__(256) void frame_losses_kernel(FrameLossArgs a, DybR
   }
   __shared__ S sAA[ND], sD[NG][ND], sRow[NG][ND], sCol[NG][ND], sG[ND];
   __shared__ float sQ[NG];
-  __shared__ S sCamG[NJ][3];
-  __shared__ float sL2d[NJ];
+  __shared__ S sCamG[NKP_MAX][3];
+  __shared__ float sL2d[NKP_MAX];
   __shared__ int sBest;
   const int b = blockIdx.x, t = threadIdx.x;
   const float invB = 1.0f / (float)a.B;
@@ -534,22 +544,22 @@ __global__ __launch_bounds__(256) void frame_losses_kernel(FrameLossArgs a, DybR
       for (int k = 0; k < 9; ++k) a.tdrot[((size_t)b * NJ + t) * 9 + k] = td[k];
   }
 
-  // --- 2-D keypoint loss on joints 25..48
+  // --- 2-D keypoint loss on the joints of the keypoint window (gt24: 25..48)
   const size_t co = (size_t)b * a.ldc;
   const S c0 = IO::ld(a.cam, a.tcam, co), c1 = IO::ld(a.cam, a.tcam, co + 1), c2 = IO::ld(a.cam, a.tcam, co + 2);
   const S den = IMG_RES * c0 + 1e-9f;
   const S tz = 2.f * FOCAL / den;
   for (int i = t; i < NJ49 * 3; i += 256) IO::st(a.djoints, a.tdjoints, (size_t)b * NJ49 * 3 + i, dyb_lit<S>(0.f));
   __syncthreads();
-  if (t < NJ) {
-    int j = 25 + t;
+  if (t < a.kp_n) {
+    int j = a.kp_lo + t;
     const size_t p = ((size_t)b * NJ49 + j) * 3;
     const float* k = a.kp + ((size_t)b * NJ49 + j) * 3;
     S x = IO::ld(a.joints, a.tjoints, p) + c1, y = IO::ld(a.joints, a.tjoints, p + 1) + c2, z = IO::ld(a.joints, a.tjoints, p + 2) + tz;
     const float sc = FOCAL / (IMG_RES * 0.5f);
     S ex = sc * (x / z) - k[0], ey = sc * (y / z) - k[1];
     float conf = k[2];
-    float norm = invB / (float)(NJ * 2);
+    float norm = invB / (float)(a.kp_n * 2);
     sL2d[t] = conf * (dyb_val(ex) * dyb_val(ex) + dyb_val(ey) * dyb_val(ey)) * norm;
     S gx2 = a.w2d * 2.f * conf * ex * norm, gy2 = a.w2d * 2.f * conf * ey * norm;
     S gx = gx2 * sc / z, gy = gy2 * sc / z;
@@ -561,7 +571,7 @@ __global__ __launch_bounds__(256) void frame_losses_kernel(FrameLossArgs a, DybR
   if (t == 0) {
     S sx = dyb_lit<S>(0.f), sy = sx, sz = sx;
     float l2d = 0.f;
-    for (int j = 0; j < NJ; ++j) {
+    for (int j = 0; j < a.kp_n; ++j) {
       sx += sCamG[j][0]; sy += sCamG[j][1]; sz += sCamG[j][2];
       l2d += sL2d[j];
     }
@@ -598,11 +608,14 @@ __global__ void loss_fold_kernel(const float* __restrict__ parts, float* __restr
 
 // losses_out[4] = (s2dloss, shape_prior, pose_prior, weighted total) as the reference defines them
 // (means over the batch); gradients are those of the weighted total.
-extern "C" int dyb_frame_losses(const float* rotmat, const float* shape, int lds, const float* cam, int ldc,
-                                const float* joints49, const float* kp2d, const float* gmm_means,
-                                const float* gmm_prec, const float* gmm_logw, float w2d, float wshape, float wpose,
-                                float* losses_out, float* drot, float* dshape, int ldds, float* dcam, int lddc,
-                                float* djoints49, int B, void* ws, size_t ws_bytes, hipStream_t st) {
+// kp_set: 0 gt24 | 1 op25 (kp_window above); an unknown set is DYB_ERR_ARG before anything is launched
+extern "C" int dyb_frame_losses_kp(const float* rotmat, const float* shape, int lds, const float* cam, int ldc,
+                                   const float* joints49, const float* kp2d, const float* gmm_means,
+                                   const float* gmm_prec, const float* gmm_logw, float w2d, float wshape, float wpose,
+                                   float* losses_out, float* drot, float* dshape, int ldds, float* dcam, int lddc,
+                                   float* djoints49, int B, int kp_set, void* ws, size_t ws_bytes, hipStream_t st) {
+  int kp_lo, kp_n;
+  DYB_REQUIRE(kp_window(kp_set, &kp_lo, &kp_n), DYB_ERR_ARG);
   DYB_REQUIRE(rotmat && shape && cam && joints49 && kp2d && gmm_means && gmm_prec && gmm_logw, DYB_ERR_ARG);
   DYB_REQUIRE(losses_out && drot && dshape && dcam && djoints49 && ws && B > 0, DYB_ERR_ARG);
   DYB_REQUIRE(ws_bytes >= (size_t)B * 4 * sizeof(float), DYB_ERR_WORKSPACE);
@@ -612,6 +625,7 @@ extern "C" int dyb_frame_losses(const float* rotmat, const float* shape, int lds
   a.parts = reinterpret_cast<float*>(ws);
   a.drot = drot; a.dshape = dshape; a.dcam = dcam; a.djoints = djoints49;
   a.lds = lds; a.ldc = ldc; a.ldds = ldds; a.lddc = lddc; a.B = B;
+  a.kp_lo = kp_lo; a.kp_n = kp_n;
   a.w2d = w2d; a.wshape = wshape; a.wpose = wpose;
   a.trot = a.tshape = a.tcam = a.tjoints = nullptr;
   a.tdrot = a.tdshape = a.tdcam = a.tdjoints = nullptr;
@@ -621,6 +635,14 @@ extern "C" int dyb_frame_losses(const float* rotmat, const float* shape, int lds
   hipLaunchKernelGGL(loss_fold_kernel, dim3(1, 1, Rp.n), dim3(64), 0, st, (const float*)a.parts, losses_out, B, Rp);
   DYB_CHECK_LAUNCH();
   return DYB_OK;
+}
+extern "C" int dyb_frame_losses(const float* rotmat, const float* shape, int lds, const float* cam, int ldc,
+                                const float* joints49, const float* kp2d, const float* gmm_means,
+                                const float* gmm_prec, const float* gmm_logw, float w2d, float wshape, float wpose,
+                                float* losses_out, float* drot, float* dshape, int ldds, float* dcam, int lddc,
+                                float* djoints49, int B, void* ws, size_t ws_bytes, hipStream_t st) {
+  return dyb_frame_losses_kp(rotmat, shape, lds, cam, ldc, joints49, kp2d, gmm_means, gmm_prec, gmm_logw, w2d, wshape, wpose, losses_out,
+                             drot, dshape, ldds, dcam, lddc, djoints49, B, 0, ws, ws_bytes, st);
 }
 // dyb_frame_losses and, in the same launch, the tangent of its four gradients along (trotmat, tshape, tcam, tjoints49): each t-prefixed
 // array has the shape and leading dimension of its value array.  The quaternion branch of every joint and the mixture component of
@@ -643,6 +665,7 @@ extern "C" int dyb_frame_losses_jvp(const float* rotmat, const float* trotmat, c
   a.parts = reinterpret_cast<float*>(ws);
   a.drot = drot; a.dshape = dshape; a.dcam = dcam; a.djoints = djoints49;
   a.lds = lds; a.ldc = ldc; a.ldds = ldds; a.lddc = lddc; a.B = B;
+  (void)kp_window(0, &a.kp_lo, &a.kp_n);            // second order supervises the gt24 window only
   a.w2d = w2d; a.wshape = wshape; a.wpose = wpose;
   a.trot = trotmat; a.tshape = tshape; a.tcam = tcam; a.tjoints = tjoints49;
   a.tdrot = tdrot; a.tdshape = tdshape; a.tdcam = tdcam; a.tdjoints = tdjoints49;
@@ -828,7 +851,8 @@ extern "C" int dyb_pa_mpjpe(const float* pred, const float* gt, float* out, floa
 //   mode 0  mean-teacher consistency   reference base_adaptor.py:320-343 (cal_teacher_loss)
 //           5*mse(s2d, t_s2d) + 5*mse(t_s3d, s3d) + 0.001*mse(shape, t_shape) + mse(rotmat, t_rotmat)
 //   mode 1  motion                     :379-398 (cal_motion_loss): masked mse of (s2d - hist_s2d) against the keypoint motion,
-//           over the 24 GT-style joints, confidence = both frames' confidences are 1
+//           over the joints of the keypoint window (gt24: the 24 GT-style joints; op25: dynaboa_webcam.py:164-182), confidence =
+//           both frames' confidences are 1
 //   mode 2  labelled exemplar          :346-376 (adapt_on_labeled_data) + :412-422 (cal_s3d_loss, hip-centred):
 //           5*l2d + 5*l3d + 0.001*mse(shape, betas) + mse(rotmat, rodrigues(pose))
 // "s2d" is the [-1,1]-normalised projection of the 49 joints with the predicted camera (:160-170), formed here.  Gradients are
@@ -840,6 +864,7 @@ extern "C" int dyb_pa_mpjpe(const float* pred, const float* gt, float* out, floa
 #define AUX_MAXB 16
 struct AuxArgs {
   int mode, B, accumulate;
+  int kp_lo, kp_n;                                // mode 1: keypoint window of the motion term (modes 0 and 2 do not read it)
   float weight;
   const float *rot, *shape, *cam, *joints;        // student pass (shape / cam rows have stride lds / ldc)
   int lds, ldc;
@@ -884,7 +909,7 @@ __global__ __launch_bounds__(256) void aux_terms_kernel(AuxArgs a, DybRep Rp) {
   const float w = a.weight;
   const float k2 = FOCAL / (IMG_RES * 0.5f);
   float l2d = 0.f, l3d = 0.f, lsh = 0.f, lpo = 0.f;
-  const float n2d = (a.mode == 0) ? (float)(B * NJ49 * 2) : (float)(B * 24 * 2);
+  const float n2d = (a.mode == 0) ? (float)(B * NJ49 * 2) : (a.mode == 1) ? (float)(B * a.kp_n * 2) : (float)(B * 24 * 2);
   const float n3d = (a.mode == 0) ? (float)(B * NJ49 * 3) : (float)(B * 24 * 3);
   if (a.mode == 2) {
     // hip centres first: pred - (pred[2] + pred[3]) / 2 over the 24 GT-style joints (49-joint indices 25 + j)
@@ -913,7 +938,7 @@ __global__ __launch_bounds__(256) void aux_terms_kernel(AuxArgs a, DybRep Rp) {
         g3[k] = w * 5.f * 2.f * d / n3d;
       }
     } else if (a.mode == 1) {
-      if (j >= 25) {
+      if (j >= a.kp_lo && j < a.kp_lo + a.kp_n) {
         aux_project(a.cam2 + (size_t)b * a.ldc2, a.joints2 + (size_t)i * 3, hu, hv, hx, hy, hz);
         const float* kc = a.kp + (size_t)i * 3;
         const float* kh = a.kp2 + (size_t)i * 3;
@@ -1029,21 +1054,74 @@ __global__ __launch_bounds__(256) void aux_terms_kernel(AuxArgs a, DybRep Rp) {
     }
   }
 }
-// mode 0 teacher / 1 motion / 2 labelled exemplar (see above).  Unused pointers may be NULL.  B <= 16.
-extern "C" int dyb_aux_loss_terms(int mode, int B, int accumulate, float weight, const float* rot, const float* shape, int lds,
-                                  const float* cam, int ldc, const float* joints49, const float* rot2, const float* shape2,
-                                  int lds2, const float* cam2, int ldc2, const float* joints2, const float* kp, const float* kp2,
-                                  const float* gt_rot, const float* gt_betas, const float* gt_s3d, float* vals5, float* d_rot,
-                                  float* d_shape, float* d_cam, float* d_joints49, float* d_cam2, float* d_joints2, hipStream_t st) {
+// mode 0 teacher / 1 motion / 2 labelled exemplar (see above).  Unused pointers may be NULL.  B <= 16.  kp_set (0 gt24 | 1 op25): the
+// motion term's keypoint window; checked for every mode, read by mode 1 only.
+extern "C" int dyb_aux_loss_terms_kp(int mode, int B, int accumulate, float weight, const float* rot, const float* shape, int lds,
+                                     const float* cam, int ldc, const float* joints49, const float* rot2, const float* shape2,
+                                     int lds2, const float* cam2, int ldc2, const float* joints2, const float* kp, const float* kp2,
+                                     const float* gt_rot, const float* gt_betas, const float* gt_s3d, float* vals5, float* d_rot,
+                                     float* d_shape, float* d_cam, float* d_joints49, float* d_cam2, float* d_joints2, int kp_set,
+                                     hipStream_t st) {
+  int kp_lo, kp_n;
+  DYB_REQUIRE(kp_window(kp_set, &kp_lo, &kp_n), DYB_ERR_ARG);
   DYB_REQUIRE(mode >= 0 && mode <= 2 && B > 0 && B <= AUX_MAXB, DYB_ERR_UNSUPPORTED);
   DYB_REQUIRE(rot && shape && cam && joints49 && vals5 && d_rot && d_shape && d_cam && d_joints49, DYB_ERR_ARG);
   if (mode == 0) DYB_REQUIRE(rot2 && shape2 && cam2 && joints2, DYB_ERR_ARG);
   if (mode == 1) DYB_REQUIRE(cam2 && joints2 && kp && kp2 && d_cam2 && d_joints2, DYB_ERR_ARG);
   if (mode == 2) DYB_REQUIRE(kp && gt_rot && gt_betas && gt_s3d, DYB_ERR_ARG);
-  AuxArgs a{mode, B, accumulate, weight, rot, shape, cam, joints49, lds, ldc, rot2, shape2, cam2, joints2, lds2, ldc2, kp, kp2,
+  AuxArgs a{mode, B, accumulate, kp_lo, kp_n, weight, rot, shape, cam, joints49, lds, ldc, rot2, shape2, cam2, joints2, lds2, ldc2, kp, kp2,
             gt_rot, gt_betas, gt_s3d, vals5, d_rot, d_shape, d_cam, d_joints49, d_cam2, d_joints2};
   const DybRep& Rp = dyb_rep_current();
   hipLaunchKernelGGL(aux_terms_kernel, dim3(1, 1, Rp.n), dim3(256), 0, st, a, Rp);
   DYB_CHECK_LAUNCH();
   return DYB_OK;
+}
+extern "C" int dyb_aux_loss_terms(int mode, int B, int accumulate, float weight, const float* rot, const float* shape, int lds,
+                                  const float* cam, int ldc, const float* joints49, const float* rot2, const float* shape2,
+                                  int lds2, const float* cam2, int ldc2, const float* joints2, const float* kp, const float* kp2,
+                                  const float* gt_rot, const float* gt_betas, const float* gt_s3d, float* vals5, float* d_rot,
+                                  float* d_shape, float* d_cam, float* d_joints49, float* d_cam2, float* d_joints2, hipStream_t st) {
+  return dyb_aux_loss_terms_kp(mode, B, accumulate, weight, rot, shape, lds, cam, ldc, joints49, rot2, shape2, lds2, cam2, ldc2, joints2, kp,
+                               kp2, gt_rot, gt_betas, gt_s3d, vals5, d_rot, d_shape, d_cam, d_joints49, d_cam2, d_joints2, 0, st);
+}
+
+// ---- tests / lab: the two windowed loss heads for nrep sequence replicas in ONE launch (what the native stepper's launches look like).
+// blob = [nrep] x blob_floats floats, per replica (B samples):
+//   frame head   rot [B][216] | shape [B][10] | cam [B][3] | joints [B][147] | kp [B][147] | losses [4] | drot [B][216] | dshape [B][10] |
+//                dcam [B][3] | djoints [B][147] | workspace [B][4]
+//   motion term  rot [B][216] | shape [B][10] | cam [B][3] | joints [B][147] | cam2 [B][3] | joints2 [B][147] | kp [B][147] | kp2 [B][147] |
+//                vals [8] | d_rot [B][216] | d_shape [B][10] | d_cam [B][3] | d_joints [B][147] | d_cam2 [B][3] | d_joints2 [B][147]
+static void loss_blob_scope(DybRep& Rp, float* blob, size_t blob_floats, int nrep) {
+  Rp.n = nrep;
+  dyb_rep_identity(Rp);
+  Rp.lo[0] = reinterpret_cast<const char*>(blob); Rp.span[0] = blob_floats * sizeof(float); Rp.stride[0] = blob_floats * sizeof(float);
+  Rp.narenas = 1;
+}
+extern "C" int dyb_debug_frame_losses_kp_replicas(float* blob, size_t blob_floats, int nrep, const float* gmm_means, const float* gmm_prec,
+                                                  const float* gmm_logw, float w2d, float wshape, float wpose, int B, int kp_set,
+                                                  hipStream_t st) {
+  DYB_REQUIRE(blob && nrep >= 1 && nrep <= DYB_MAX_REPLICAS && B > 0, DYB_ERR_ARG);
+  const size_t b = (size_t)B;
+  DYB_REQUIRE(blob_floats >= b * (216 + 10 + 3 + 147 + 147) + 4 + b * (216 + 10 + 3 + 147 + 4), DYB_ERR_WORKSPACE);
+  float *rot = blob, *shape = rot + b * 216, *cam = shape + b * 10, *joints = cam + b * 3, *kp = joints + b * 147, *losses = kp + b * 147,
+        *drot = losses + 4, *dshape = drot + b * 216, *dcam = dshape + b * 10, *djoints = dcam + b * 3, *ws = djoints + b * 147;
+  DybRep Rp{};
+  loss_blob_scope(Rp, blob, blob_floats, nrep);
+  DybRepScope scope(Rp);
+  return dyb_frame_losses_kp(rot, shape, 10, cam, 3, joints, kp, gmm_means, gmm_prec, gmm_logw, w2d, wshape, wpose, losses, drot, dshape, 10,
+                             dcam, 3, djoints, B, kp_set, ws, b * 4 * sizeof(float), st);
+}
+extern "C" int dyb_debug_motion_term_kp_replicas(float* blob, size_t blob_floats, int nrep, int B, int accumulate, float weight, int kp_set,
+                                                 hipStream_t st) {
+  DYB_REQUIRE(blob && nrep >= 1 && nrep <= DYB_MAX_REPLICAS && B > 0, DYB_ERR_ARG);
+  const size_t b = (size_t)B;
+  DYB_REQUIRE(blob_floats >= b * (216 + 10 + 3 + 147 + 3 + 147 + 147 + 147) + 8 + b * (216 + 10 + 3 + 147 + 3 + 147), DYB_ERR_WORKSPACE);
+  float *rot = blob, *shape = rot + b * 216, *cam = shape + b * 10, *joints = cam + b * 3, *cam2 = joints + b * 147, *joints2 = cam2 + b * 3,
+        *kp = joints2 + b * 147, *kp2 = kp + b * 147, *vals = kp2 + b * 147, *d_rot = vals + 8, *d_shape = d_rot + b * 216,
+        *d_cam = d_shape + b * 10, *d_joints = d_cam + b * 3, *d_cam2 = d_joints + b * 147, *d_joints2 = d_cam2 + b * 3;
+  DybRep Rp{};
+  loss_blob_scope(Rp, blob, blob_floats, nrep);
+  DybRepScope scope(Rp);
+  return dyb_aux_loss_terms_kp(1, B, accumulate, weight, rot, shape, 10, cam, 3, joints, nullptr, nullptr, 0, cam2, 3, joints2, kp, kp2, nullptr,
+                               nullptr, nullptr, vals, d_rot, d_shape, d_cam, d_joints, d_cam2, d_joints2, kp_set, st);
 }

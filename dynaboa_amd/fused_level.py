@@ -75,7 +75,7 @@ def _p(t):
 
 class _LevelFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, theta, image, init_state, kp2d, smpl, prior, w2d, wshape, wpose, n_iter, need_feature):
+    def forward(ctx, theta, image, init_state, kp2d, smpl, prior, w2d, wshape, wpose, n_iter, need_feature, kp_set=0):
         lib = _lib.load()
         B, _, H, W = image.shape
         L = get_layout(B, H, W)
@@ -104,11 +104,11 @@ class _LevelFunction(torch.autograd.Function):
         verts, joints, saved, losses, drot_l, dshape_l, dcam_l, djoints_l, lws = parts
         check(lib.dyb_lbs_fwd(smpl._pf, smpl._pi, shape.data_ptr(), STATE_LD, rot.data_ptr(), verts.data_ptr(), joints.data_ptr(),
                               saved.data_ptr(), B, st), "dyb_lbs_fwd")
-        check(lib.dyb_frame_losses(rot.data_ptr(), shape.data_ptr(), STATE_LD, cam.data_ptr(), STATE_LD, joints.data_ptr(),
-                                   kp2d.data_ptr(), prior.means.data_ptr(), prior.precisions.data_ptr(),
-                                   prior.log_nll_weights.data_ptr(), float(w2d), float(wshape), float(wpose), losses.data_ptr(),
-                                   drot_l.data_ptr(), dshape_l.data_ptr(), 10, dcam_l.data_ptr(), 3, djoints_l.data_ptr(), B,
-                                   lws.data_ptr(), B * 16, st), "dyb_frame_losses")
+        check(lib.dyb_frame_losses_kp(rot.data_ptr(), shape.data_ptr(), STATE_LD, cam.data_ptr(), STATE_LD, joints.data_ptr(),
+                                      kp2d.data_ptr(), prior.means.data_ptr(), prior.precisions.data_ptr(),
+                                      prior.log_nll_weights.data_ptr(), float(w2d), float(wshape), float(wpose), losses.data_ptr(),
+                                      drot_l.data_ptr(), dshape_l.data_ptr(), 10, dcam_l.data_ptr(), 3, djoints_l.data_ptr(), B,
+                                      int(kp_set), lws.data_ptr(), B * 16, st), "dyb_frame_losses_kp")
         ctx.L, ctx.n_iter, ctx.smpl, ctx.B = L, n_iter, smpl, B
         ctx.set_materialize_grads(False)            # unused outputs arrive as None in backward (handled there), not as zero-filled tensors
         _LAST_FORWARD[(B, H, W, str(dev))] = (_fwd_key(theta, image, init_state, n_iter), acts, theta, image, init_state)
@@ -153,10 +153,11 @@ class _LevelFunction(torch.autograd.Function):
         check(lib.dyb_hmr_backward(L.plan, theta.data_ptr(), acts.data_ptr(), eng["d_rot"].data_ptr(), eng["d_state"].data_ptr(),
                                    ctx.n_iter, eng["grads"].data_ptr(), ws.data_ptr(), L.ws_bytes, st, aux_stream_of(theta)),
               "dyb_hmr_backward")
-        return (eng["grads"].clone(),) + (None,) * 10
+        return (eng["grads"].clone(),) + (None,) * 11
 
 
-def level_forward(model, smpl, prior, image, kp2d, w2d, wshape, wpose, n_iter: int = 3, need_feature: bool = True):
+def level_forward(model, smpl, prior, image, kp2d, w2d, wshape, wpose, n_iter: int = 3, need_feature: bool = True,
+                  kp_set: str = "gt24"):
     """``model``: an ``HMR`` or a ``MAML`` wrapper / learner around one.  Returns
     ``(loss_total, comps(s2d, shape_prior, pose_prior), rotmat, shape, cam, joints49, verts, features)`` -
     ``loss_total`` and the five outputs are differentiable w.r.t. the (fast) weights."""
@@ -168,5 +169,6 @@ def level_forward(model, smpl, prior, image, kp2d, w2d, wshape, wpose, n_iter: i
         raise NotImplementedError("the fused level node is the eval-mode path (the adaptation loop runs model.eval(), "
                                   "dynaboa_benchmark.py:89); in train() mode use fused_level=0 / the HMR module directly")
     st0 = hmr.make_init_state(image.shape[0])
-    out = _LevelFunction.apply(theta, image, st0, kp2d, smpl, prior, w2d, wshape, wpose, n_iter, need_feature)
+    from .losses import kp_set_id
+    out = _LevelFunction.apply(theta, image, st0, kp2d, smpl, prior, w2d, wshape, wpose, n_iter, need_feature, kp_set_id(kp_set))
     return out[0], out[1], out[2], out[3], out[4], out[5], out[6], list(out[7:])

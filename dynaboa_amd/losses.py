@@ -64,9 +64,37 @@ class _GmmPrior(torch.autograd.Function):
         return dpose * g.reshape(-1, 1), None
 
 
+# Keypoint sets (include/dynaboa_hip.h DYB_KP_*): the window of the 49-joint convention that the 2-D keypoint term and the motion term
+# supervise - "gt24" joints 25..48 (ground-truth style, dynaboa_benchmark.py), "op25" joints 0..24 (OpenPose BODY_25 detections, the
+# online path of dynaboa_webcam.py:164-182, :206, :248).
+KP_SETS = {"gt24": 0, "op25": 1}
+KP_WINDOWS = {"gt24": (25, 24), "op25": (0, 25)}         # (first joint, count)
+
+
+def kp_set_id(kp_set) -> int:
+    """'gt24' | 'op25' -> the library's code; anything else is an error here, before any call."""
+    if kp_set not in KP_SETS:
+        raise ValueError(f"unknown keypoint set {kp_set!r}: one of {sorted(KP_SETS)}")
+    return KP_SETS[kp_set]
+
+
+def kp_set_refusal(o) -> Optional[str]:
+    """None, or why these options cannot run with their keypoint set: the second derivative of the loss head exists for the gt24
+    window only (csrc/losses.hip dyb_frame_losses_jvp, csrc/head_hvp.hip)."""
+    kp_set = getattr(o, "kp_set", "gt24")
+    kp_set_id(kp_set)
+    if kp_set == "gt24":
+        return None
+    if getattr(o, "second_order", 0):
+        return f"second_order with kp_set {kp_set}: second-order MAML differentiates the loss head twice, which exists for gt24 only"
+    if getattr(o, "hvp_head", "fd") == "closed":
+        return f"--hvp_head closed with kp_set {kp_set}: the closed-form second derivative of the frame head covers gt24 only"
+    return None
+
+
 class _FrameLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rotmat, shape, cam, joints, kp2d, prior, w2d, wshape, wpose):
+    def forward(ctx, rotmat, shape, cam, joints, kp2d, prior, w2d, wshape, wpose, kp_set=0):
         lib = _lib.load()
         B = rotmat.shape[0]
         dev = rotmat.device
@@ -79,11 +107,12 @@ class _FrameLoss(torch.autograd.Function):
         dcam = torch.empty(B, 3, device=dev)
         djoints = torch.empty(B, 49, 3, device=dev)
         ws = torch.empty(B * 4, device=dev)
-        check(lib.dyb_frame_losses(rotmat.data_ptr(), shape.data_ptr(), shape.stride(0), cam.data_ptr(), cam.stride(0),
-                                   joints.data_ptr(), kp2d.data_ptr(), prior.means.data_ptr(), prior.precisions.data_ptr(),
-                                   prior.log_nll_weights.data_ptr(), float(w2d), float(wshape), float(wpose),
-                                   losses.data_ptr(), drot.data_ptr(), dshape.data_ptr(), 10, dcam.data_ptr(), 3,
-                                   djoints.data_ptr(), B, ws.data_ptr(), B * 16, stream_of(rotmat)), "dyb_frame_losses")
+        check(lib.dyb_frame_losses_kp(rotmat.data_ptr(), shape.data_ptr(), shape.stride(0), cam.data_ptr(), cam.stride(0),
+                                      joints.data_ptr(), kp2d.data_ptr(), prior.means.data_ptr(), prior.precisions.data_ptr(),
+                                      prior.log_nll_weights.data_ptr(), float(w2d), float(wshape), float(wpose),
+                                      losses.data_ptr(), drot.data_ptr(), dshape.data_ptr(), 10, dcam.data_ptr(), 3,
+                                      djoints.data_ptr(), B, int(kp_set), ws.data_ptr(), B * 16, stream_of(rotmat)),
+              "dyb_frame_losses_kp")
         ctx.save_for_backward(drot, dshape, dcam, djoints)
         comps = losses[:3].clone()
         ctx.mark_non_differentiable(comps)
@@ -92,12 +121,13 @@ class _FrameLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_total, _g_comps):
         drot, dshape, dcam, djoints = ctx.saved_tensors
-        return drot * g_total, dshape * g_total, dcam * g_total, djoints * g_total, None, None, None, None, None
+        return drot * g_total, dshape * g_total, dcam * g_total, djoints * g_total, None, None, None, None, None, None
 
 
-def frame_losses(rotmat, shape, cam, joints49, kp2d, prior: MaxMixturePrior, w2d, wshape, wpose):
-    """-> (weighted total [differentiable], tensor(s2dloss, shape_prior, pose_prior) [logging only])."""
-    return _FrameLoss.apply(rotmat, shape, cam, joints49, kp2d, prior, w2d, wshape, wpose)
+def frame_losses(rotmat, shape, cam, joints49, kp2d, prior: MaxMixturePrior, w2d, wshape, wpose, kp_set: str = "gt24"):
+    """-> (weighted total [differentiable], tensor(s2dloss, shape_prior, pose_prior) [logging only]).  kp_set: the joints of the
+    [B][49][3] keypoint array the 2-D term supervises (KP_SETS)."""
+    return _FrameLoss.apply(rotmat, shape, cam, joints49, kp2d, prior, w2d, wshape, wpose, kp_set_id(kp_set))
 
 
 def pose_prior(rotmat, prior: MaxMixturePrior):
@@ -146,7 +176,7 @@ class _AuxTerms(torch.autograd.Function):
     (cam2, joints2)."""
 
     @staticmethod
-    def forward(ctx, mode, rot, shape, cam, joints, rot2, shape2, cam2, joints2, kp, kp2, gt_rot, gt_betas, gt_s3d):
+    def forward(ctx, mode, rot, shape, cam, joints, rot2, shape2, cam2, joints2, kp, kp2, gt_rot, gt_betas, gt_s3d, kp_set=0):
         lib = _lib.load()
         B = rot.shape[0]
         dev = rot.device
@@ -160,10 +190,10 @@ class _AuxTerms(torch.autograd.Function):
         f = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
         vals, d_rot, d_shape, d_cam, d_joints = f(5), f(B, 24, 3, 3), f(B, 10), f(B, 3), f(B, 49, 3)
         d_cam2, d_joints2 = (f(B, 3), f(B, 49, 3)) if mode == 1 else (None, None)
-        check(lib.dyb_aux_loss_terms(mode, B, 0, 1.0, rot.data_ptr(), shape.data_ptr(), ld(shape), cam.data_ptr(), ld(cam), joints.data_ptr(),
-                                     p(rot2), p(shape2), ld(shape2), p(cam2), ld(cam2), p(joints2), p(kp), p(kp2), p(gt_rot), p(gt_betas),
-                                     p(gt_s3d), vals.data_ptr(), d_rot.data_ptr(), d_shape.data_ptr(), d_cam.data_ptr(),
-                                     d_joints.data_ptr(), p(d_cam2), p(d_joints2), stream_of(rot)), "dyb_aux_loss_terms")
+        check(lib.dyb_aux_loss_terms_kp(mode, B, 0, 1.0, rot.data_ptr(), shape.data_ptr(), ld(shape), cam.data_ptr(), ld(cam), joints.data_ptr(),
+                                        p(rot2), p(shape2), ld(shape2), p(cam2), ld(cam2), p(joints2), p(kp), p(kp2), p(gt_rot), p(gt_betas),
+                                        p(gt_s3d), vals.data_ptr(), d_rot.data_ptr(), d_shape.data_ptr(), d_cam.data_ptr(),
+                                        d_joints.data_ptr(), p(d_cam2), p(d_joints2), int(kp_set), stream_of(rot)), "dyb_aux_loss_terms_kp")
         ctx.mode = mode
         ctx.save_for_backward(*(t for t in (d_rot, d_shape, d_cam, d_joints, d_cam2, d_joints2) if t is not None))
         comps = vals[:4].clone()
@@ -177,22 +207,22 @@ class _AuxTerms(torch.autograd.Function):
         out = [None, d_rot * g, d_shape * g, d_cam * g, d_joints * g, None, None, None, None]
         if ctx.mode == 1:
             out[7], out[8] = saved[4] * g, saved[5] * g
-        return tuple(out) + (None,) * 5
+        return tuple(out) + (None,) * 6
 
 
 AUX_MAX_BATCH = 16          # dyb_aux_loss_terms: one launch covers up to 16 samples
 
 
-def _aux(mode, batched, const):
+def _aux(mode, batched, const, kp_set=0):
     """`batched`: 13 per-sample tensors (or None) in _AuxTerms.forward's order.  Every component is a mean over the batch, so a batch
     beyond one launch's 16 samples is the size-weighted sum of its chunks."""
     B = batched[0].shape[0]
     if B <= AUX_MAX_BATCH:
-        return _AuxTerms.apply(mode, *batched)
+        return _AuxTerms.apply(mode, *batched, kp_set)
     loss, comps = None, None
     for i in range(0, B, AUX_MAX_BATCH):
         part = [None if t is None else t[i:i + AUX_MAX_BATCH] for t in batched]
-        l, c = _AuxTerms.apply(mode, *part)
+        l, c = _AuxTerms.apply(mode, *part, kp_set)
         wgt = part[0].shape[0] / B
         loss = l * wgt if loss is None else loss + l * wgt
         comps = c * wgt if comps is None else comps + c * wgt
@@ -205,10 +235,11 @@ def teacher_term(rot, shape, cam, joints49, t_rot, t_shape, t_cam, t_joints49):
     return _aux(0, [rot, shape, cam, joints49, t_rot, t_shape, t_cam, t_joints49, None, None, None, None, None], None)
 
 
-def motion_term(rot, shape, cam, joints49, h_cam, h_joints49, kp2d, hist_kp2d):
-    """Motion term (base_adaptor.py:379-398): confidence-masked mse between the predicted and the annotated keypoint motion from the
-    history frame to this one; differentiable in both passes -> (loss, components)."""
-    return _aux(1, [rot, shape, cam, joints49, None, None, h_cam, h_joints49, kp2d, hist_kp2d, None, None, None], None)
+def motion_term(rot, shape, cam, joints49, h_cam, h_joints49, kp2d, hist_kp2d, kp_set: str = "gt24"):
+    """Motion term (base_adaptor.py:379-398; with kp_set "op25" dynaboa_webcam.py:164-182): confidence-masked mse between the
+    predicted and the annotated keypoint motion from the history frame to this one, over the joints of the keypoint set;
+    differentiable in both passes -> (loss, components)."""
+    return _aux(1, [rot, shape, cam, joints49, None, None, h_cam, h_joints49, kp2d, hist_kp2d, None, None, None], None, kp_set_id(kp_set))
 
 
 def labelled_term(rot, shape, cam, joints49, kp2d, gt_rot, gt_betas, gt_s3d):

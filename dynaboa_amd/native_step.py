@@ -17,6 +17,7 @@ import torch
 from . import _lib
 from ._abi import check
 from .hmr import get_layout, stream_of
+from .losses import kp_set_id
 
 
 def coverage(o, have_bundle: bool = True):
@@ -99,6 +100,10 @@ class NativeStepper:
         self.mode = mode(o, getattr(adaptor, "bundle", None) is not None)
         self.full = self.mode == "full"
         si("inner_step", self.K); si("eval_lower", self.eval_lower); si("n_iter", 3)
+        si("kp_set", kp_set_id(getattr(o, "kp_set", "gt24")))
+        # metrics = 0 (the online path: no ground truth): no metric records, the gt_pose / gt_betas / gender inputs stay NULL
+        self.metrics = int(getattr(o, "metrics", 1))
+        si("metrics", self.metrics)
         if self.full:
             g = lambda k, d=0: getattr(o, k, d)
             si("full", 1)
@@ -305,24 +310,28 @@ class NativeStepper:
         """One frame per replica (`batches`: list of S batch dicts).  -> (frame index, first record slot)."""
         if len(batches) != self.S:
             raise ValueError(f"{self.S} replicas, {len(batches)} batches")
-        rows = {r: [b["image"].contiguous().float(), b["smpl_j2d"].contiguous().float(), b["pose"].contiguous().float(),
-                    b["betas"].contiguous().float(), b["gender"].contiguous().long()] for r, b in enumerate(batches)}
+        rows = {r: [b["image"].contiguous().float(), b["smpl_j2d"].contiguous().float()] + self._gt_row(b) for r, b in enumerate(batches)}
         side = None
         if side_stream is not None and self.use_side:
             side = side_stream.cuda_stream
             for row in rows.values():
                 for t in row:
-                    if t.is_cuda:
+                    if t is not None and t.is_cuda:
                         t.record_stream(side_stream)
         return self._step(rows, False, side)[:2]
 
     def adapt_frame(self, batch: Dict[str, torch.Tensor], side_stream=None):
         return self.adapt_frames([batch], side_stream)
 
-    @staticmethod
-    def _full_row(batch, hist, exemplars):
+    def _gt_row(self, batch):
+        """gt_pose, gt_betas, gender of a batch - the metric records' inputs; absent (NULL) with metrics = 0."""
+        if not self.metrics:
+            return [None, None, None]
+        return [batch["pose"].contiguous().float(), batch["betas"].contiguous().float(), batch["gender"].contiguous().long()]
+
+    def _full_row(self, batch, hist, exemplars):
         c = lambda t: t if (t.dtype is torch.float32 and t.is_contiguous()) else t.contiguous().float()      # (no new view objects on the common path)
-        row = [c(batch["image"]), c(batch["smpl_j2d"]), c(batch["pose"]), c(batch["betas"]), batch["gender"].contiguous().long()]
+        row = [c(batch["image"]), c(batch["smpl_j2d"])] + self._gt_row(batch)
         row += [c(hist[0]), c(hist[1])] if hist is not None else [None, None]
         row += [c(exemplars[k]) for k in ("img", "keypoints", "pose", "betas", "pose_3d")] if exemplars is not None else [None] * 5
         return row

@@ -275,6 +275,20 @@ int dyb_frame_losses(const float* rotmat, const float* shape, int lds, const flo
                      const float* kp2d, const float* gmm_means, const float* gmm_prec, const float* gmm_logw, float w2d,
                      float wshape, float wpose, float* losses_out, float* drot, float* dshape, int ldds, float* dcam,
                      int lddc, float* djoints49, int B, void* ws, size_t ws_bytes, dyb_stream_t stream);
+/* Keypoint sets: the window of the 49-joint convention that the 2-D keypoint term of the frame head and the motion term supervise.
+ * The keypoint array keeps its [B][49][3] layout for both.
+ *   DYB_KP_GT24 (0): joints 25..48, mean over B * 24 * 2 - the ground-truth style joints of dynaboa_benchmark.py (base_adaptor.py:229,234)
+ *   DYB_KP_OP25 (1): joints  0..24, mean over B * 25 * 2 - OpenPose BODY_25 detections in slots 0..24, the online path of
+ *                    dynaboa_webcam.py (:164-182 cal_motion_loss, :206 / :248 the frame term on [:, :25])
+ * dyb_frame_losses_kp is dyb_frame_losses with the set as an argument (value, the four gradients and the per-sample camera sum all
+ * follow the window; dyb_frame_losses forwards with DYB_KP_GT24 and its results are unchanged bit for bit).  An unknown set returns
+ * DYB_ERR_ARG before anything is launched. */
+#define DYB_KP_GT24 0
+#define DYB_KP_OP25 1
+int dyb_frame_losses_kp(const float* rotmat, const float* shape, int lds, const float* cam, int ldc, const float* joints49,
+                        const float* kp2d, const float* gmm_means, const float* gmm_prec, const float* gmm_logw, float w2d,
+                        float wshape, float wpose, float* losses_out, float* drot, float* dshape, int ldds, float* dcam,
+                        int lddc, float* djoints49, int B, int kp_set, void* ws, size_t ws_bytes, dyb_stream_t stream);
 
 /* ---- closed-form second derivative of the frame-loss head (--hvp exact --hvp_head closed).
  * Every *_jvp entry point computes what its sibling computes AND, in the same launches, the directional derivative along the
@@ -328,6 +342,23 @@ int dyb_aux_loss_terms(int mode, int B, int accumulate, float weight, const floa
                        const float* cam2, int ldc2, const float* joints2, const float* kp, const float* kp2,
                        const float* gt_rot, const float* gt_betas, const float* gt_s3d, float* vals5, float* d_rot,
                        float* d_shape, float* d_cam, float* d_joints49, float* d_cam2, float* d_joints2, dyb_stream_t stream);
+/* The same with a keypoint set (see dyb_frame_losses_kp) for the motion term: both passes' projections, the mask "both frames'
+ * confidences are 1", the mean over B * count * 2 and the gradients to the student and the history pass are restricted to the
+ * window.  Modes 0 and 2 do not read it (an unknown set is DYB_ERR_ARG for every mode).  dyb_aux_loss_terms forwards with DYB_KP_GT24. */
+int dyb_aux_loss_terms_kp(int mode, int B, int accumulate, float weight, const float* rot, const float* shape, int lds,
+                          const float* cam, int ldc, const float* joints49, const float* rot2, const float* shape2, int lds2,
+                          const float* cam2, int ldc2, const float* joints2, const float* kp, const float* kp2,
+                          const float* gt_rot, const float* gt_betas, const float* gt_s3d, float* vals5, float* d_rot,
+                          float* d_shape, float* d_cam, float* d_joints49, float* d_cam2, float* d_joints2, int kp_set,
+                          dyb_stream_t stream);
+/* tests / lab: the two windowed heads for nrep sequence replicas in one launch, each replica with its own inputs and outputs in its
+ * slice of `blob` ([nrep][blob_floats]; per-replica layouts in csrc/losses.hip).  Results per replica are those of the call on that
+ * replica alone. */
+int dyb_debug_frame_losses_kp_replicas(float* blob, size_t blob_floats, int nrep, const float* gmm_means, const float* gmm_prec,
+                                       const float* gmm_logw, float w2d, float wshape, float wpose, int B, int kp_set,
+                                       dyb_stream_t stream);
+int dyb_debug_motion_term_kp_replicas(float* blob, size_t blob_floats, int nrep, int B, int accumulate, float weight, int kp_set,
+                                      dyb_stream_t stream);
 
 /* Gradient assembly of the fused HMR + SMPL + frame-loss node (one autograd node per adaptation level instead
  * of three plus glue): out = g*a (+ ext) with g a device scalar (NULL = 1), and the d_rotmat / d_state inputs of
