@@ -448,6 +448,49 @@ class BaseAdaptor:
             cache[key] = Renderer(resolution=key, orig_img=True, wireframe=False, faces=self.smpl_neutral.faces, device=self.device)
         return cache[key]
 
+    def ragged_renderer(self):
+        """The renderer behind the ragged launches (every mesh brings its own frame size: its resolution is not used)."""
+        r = self.__dict__.get("_ragged_renderer")
+        if r is None:
+            from .render import Renderer
+            r = self._ragged_renderer = Renderer(resolution=(224, 224), orig_img=True, wireframe=False, faces=self.smpl_neutral.faces,
+                                                 device=self.device)
+        return r
+
+    def result_step(self):
+        """The number this frame's result files carry: `global_step`, unless the driver numbers them otherwise (the sharded driver
+        with several sequences per GPU: the global frame index - its adaptors share one exppath)."""
+        n = getattr(self, "_result_step", None)
+        return self.global_step if n is None else n
+
+    def overlay_jobs(self, vts, cam, images, name, bbox, prefix=None):
+        """The overlays save_results writes for this batch, not drawn yet: [(frame uint8 (H, W, 3) on the device, vertices
+        (6890, 3), camera (4,) = (sx, sy, tx, ty), path)] - over the original frame files when they exist, else over the
+        de-normalised crops.  A group collects the jobs of all its sequences and draws them in one ragged launch (draw_overlays)."""
+        from .render import convert_crop_cam_to_orig_img
+        vts, cam = vts.detach(), cam.detach().float()
+        outdir = os.path.join(self.exppath, "image")
+        os.makedirs(outdir, exist_ok=True)
+        B = vts.shape[0]
+        paths = [os.path.join(outdir, f"{prefix}_{self.result_step() + i}.png") for i in range(B)]
+        imgdir = getattr(self, "imgdir", None)
+        files = [os.path.join(imgdir, n) for n in name] if (name is not None and bbox is not None and imgdir is not None) else None
+        if files is not None and all(os.path.isfile(f) for f in files):
+            from .datasets import read_image
+            bbox = bbox.detach().to(cam.device).float()
+            jobs = []
+            for i, f in enumerate(files):
+                frame = torch.from_numpy(read_image(f)).to(self.device)
+                h, w = int(frame.shape[0]), int(frame.shape[1])
+                ocam = convert_crop_cam_to_orig_img(cam[i:i + 1], bbox[i:i + 1], w, h)
+                jobs.append((frame, vts[i], ocam[0], paths[i]))
+            return jobs
+        mean = torch.tensor(constants.IMG_NORM_MEAN, device=images.device).view(1, 3, 1, 1)
+        std = torch.tensor(constants.IMG_NORM_STD, device=images.device).view(1, 3, 1, 1)
+        crops = ((images.detach() * std + mean) * 255.0).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+        ccam = torch.stack([cam[:, 0], cam[:, 0], cam[:, 1], cam[:, 2]], 1)
+        return [(crops[i], vts[i], ccam[i], paths[i]) for i in range(B)]
+
     def save_results(self, vts, cam, images, name, bbox, prefix=None):
         """reference base_adaptor.py:429-443: the predicted mesh drawn over its frame, one PNG per frame of the batch at
         ``exppath/image/{prefix}_{global_step + i}.png``.  vts (B, 6890, 3), cam (B, 3) = (s, tx, ty) of the crop, images the
@@ -455,36 +498,22 @@ class BaseAdaptor:
         without image files (the synthetic bundle): the mesh is then drawn over the de-normalised crop with the crop's own camera
         (s, s, tx, ty).  Vertices, camera and frame stay on the device; only the finished picture comes to the host.
         -> the written paths."""
-        from PIL import Image
-        from .render import convert_crop_cam_to_orig_img
-        vts, cam = vts.detach(), cam.detach().float()
-        outdir = os.path.join(self.exppath, "image")
-        os.makedirs(outdir, exist_ok=True)
-        B = vts.shape[0]
-        paths = [os.path.join(outdir, f"{prefix}_{self.global_step + i}.png") for i in range(B)]
-        imgdir = getattr(self, "imgdir", None)
-        files = [os.path.join(imgdir, n) for n in name] if (name is not None and bbox is not None and imgdir is not None) else None
-        if files is not None and all(os.path.isfile(f) for f in files):
-            from .datasets import read_image
-            bbox = bbox.detach().to(cam.device).float()
-            for i, f in enumerate(files):
-                frame = torch.from_numpy(read_image(f)).to(self.device)
-                h, w = int(frame.shape[0]), int(frame.shape[1])
-                ocam = convert_crop_cam_to_orig_img(cam[i:i + 1], bbox[i:i + 1], w, h)
-                pic = self._renderer(w, h).render(frame, vts[i], ocam[0], color=self.RESULT_COLOR)
-                Image.fromarray(pic.cpu().numpy()).save(paths[i])
-            return paths
-        mean = torch.tensor(constants.IMG_NORM_MEAN, device=images.device).view(1, 3, 1, 1)
-        std = torch.tensor(constants.IMG_NORM_STD, device=images.device).view(1, 3, 1, 1)
-        crops = ((images.detach() * std + mean) * 255.0).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
-        ccam = torch.stack([cam[:, 0], cam[:, 0], cam[:, 1], cam[:, 2]], 1)
-        res = int(images.shape[-1])
-        for lo in range(0, B, 64):                                   # one launch draws up to 64 meshes
-            hi = min(lo + 64, B)
-            pics = self._renderer(res, res).render(crops[lo:hi], vts[lo:hi], ccam[lo:hi], color=self.RESULT_COLOR).cpu().numpy()
-            for i in range(lo, hi):
-                Image.fromarray(pics[i - lo]).save(paths[i])
-        return paths
+        # one ragged launch per 64 pictures, whatever their sizes (3DPW mixes 1920x1080 and 1080x1920 frames)
+        return draw_overlays(self.ragged_renderer(), self.overlay_jobs(vts, cam, images, name, bbox, prefix), self.RESULT_COLOR)
 
     def write_summaries(self, losses):
         self.last_summaries = losses
+
+
+def draw_overlays(renderer, jobs, color):
+    """Draw overlay jobs (BaseAdaptor.overlay_jobs, of one adaptor or of all sequences of a group's step) - one ragged launch per 64
+    meshes, each over its own frame at its own size - and write the PNGs.  -> the written paths."""
+    from PIL import Image
+    paths = []
+    for lo in range(0, len(jobs), 64):
+        part = jobs[lo:lo + 64]
+        pics = renderer.render_many([j[0] for j in part], [j[1] for j in part], torch.stack([j[2] for j in part]), color=color)
+        for pic, j in zip(pics, part):
+            Image.fromarray(pic.cpu().numpy()).save(j[3])
+            paths.append(j[3])
+    return paths

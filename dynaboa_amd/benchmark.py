@@ -121,6 +121,11 @@ parser.add_argument('--replica_policy', choices=['throughput', 'bitexact'], defa
                     help="--seqs_per_gpu > 1: 'throughput' = split depth chosen for the replica-multiplied grid and, from 5 sequences per "
                          "launch, the throughput schedule (results equal to a sequence adapted alone to fp32 rounding); 'bitexact' = the "
                          "single-sequence policy (bit-identical to sequences adapted alone, about half the frame rate at 32 sequences)")
+parser.add_argument('--native_results', type=int, default=0, choices=[0, 1],
+                    help='1: --save_res / --dump_predictions stay on the native frame stepper (and work with --seqs_per_gpu > 1): the '
+                         'stepper keeps each frame\'s last final inference in a result ring on the device, the overlay of a step\'s frames '
+                         'is drawn from there by one ragged launch and the dump is written from there; 0 (default): both take the run '
+                         'to the torch.autograd composition')
 parser.add_argument('--eval_lower', type=int, default=1, choices=[0, 1],
                     help='run inference() after every inner step like the reference (:142)')
 
@@ -284,7 +289,30 @@ class Adaptor(BaseAdaptor):
         if self._native.full:
             return self._adapt_native_full(batch)
         f, slot = self._native.adapt_frame(batch, side_stream=self._side)
-        return self._native_bookkeeping(f, slot)
+        out = self._native_bookkeeping(f, slot)
+        self._native_write_results(f, batch)
+        return out
+
+    def _native_write_results(self, f, batch):
+        """--native_results 1: what the autograd path's inference() leaves behind for the frame - result/Pred_{n}.pt and
+        image/Pred_{n}.png of its LAST final inference - from the stepper's result ring."""
+        ns = self._native
+        if ns.results is None:
+            return
+        ns.join()                                            # a side-stream tail owes this frame's final inference
+        res = ns.result(f, getattr(self, "_native_replica", 0))
+        if self.options.dump_predictions:
+            self.dump_prediction(res["vts"], res["cam"], res["rotmat"], res["shape"])
+        if getattr(self.options, "save_res", 0):
+            self.save_results(res["vts"], res["cam"], batch["image"], batch.get("imgname"), batch.get("bbox"), prefix="Pred")
+
+    def dump_prediction(self, vts, cam, rotmat, shape):
+        """result/Pred_{n}.pt (reference dynaboa_benchmark.py:250-254), n = result_step(): what inference() and the native path write."""
+        import joblib
+        os.makedirs(os.path.join(self.exppath, 'result'), exist_ok=True)
+        cam_t = torch.stack([cam[:, 1], cam[:, 2], 2 * 5000. / (224 * cam[:, 0] + 1e-9)], dim=-1)
+        joblib.dump({'verts': vts.cpu().numpy(), 'cam': cam_t.cpu().numpy(), 'rotmat': rotmat.cpu().numpy(), 'beta': shape.cpu().numpy()},
+                    os.path.join(self.exppath, 'result', f'Pred_{self.result_step()}.pt'))
 
     def _native_full_inputs(self, batch):
         """-> (hist, exemplars) of this frame for the native full-term stepper: the history pair of the motion term (None while
@@ -303,7 +331,9 @@ class Adaptor(BaseAdaptor):
         """The reference's full term set through the native stepper: one C call for the whole frame incl. the dynamic loop."""
         hist, ex = self._native_full_inputs(batch)
         f, slot, extra = self._native.adapt_frame_full(batch, hist, ex)
-        return self._native_full_bookkeeping(f, slot, extra, hist)
+        out = self._native_full_bookkeeping(f, slot, extra, hist)
+        self._native_write_results(f, batch)
+        return out
 
     def _native_full_bookkeeping(self, f, slot, extra, hist):
         """What adaptation() leaves behind after a full-term frame (replica `_native_replica` of the stepper)."""
@@ -540,12 +570,7 @@ class Adaptor(BaseAdaptor):
             mpjpe_t = (pred14 - gt14).norm(dim=-1).mean(dim=-1)
             pve_t = (gt_neutral - pred_vertices).norm(dim=-1).mean()
         if self.options.dump_predictions:
-            import joblib
-            os.makedirs(os.path.join(self.exppath, 'result'), exist_ok=True)
-            cam_t = torch.stack([pred_cam[:, 1], pred_cam[:, 2], 2 * 5000. / (224 * pred_cam[:, 0] + 1e-9)], dim=-1)
-            joblib.dump({'verts': pred_vertices.cpu().numpy(), 'cam': cam_t.cpu().numpy(),
-                         'rotmat': pred_rotmat.cpu().numpy(), 'beta': pred_shape.cpu().numpy()},
-                        os.path.join(self.exppath, 'result', f'Pred_{self.global_step}.pt'))
+            self.dump_prediction(pred_vertices, pred_cam, pred_rotmat, pred_shape)
         if getattr(self.options, "save_res", 0) and (tag is None or tag[0] == 'final'):
             # reference dynaboa_benchmark.py:257-258 (its call passes two arguments too many and would raise; the method's own
             # signature is used).  There every inference() of a frame writes Pred_{step}.png and the last one's file stays; here

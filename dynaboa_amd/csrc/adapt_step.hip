@@ -199,6 +199,50 @@ __global__ __launch_bounds__(1024) void feat_cos_kernel(const float* __restrict_
   }
 }
 
+// ---- result ring: one final inference packed into one row ------------------------------------------------------------------
+// Row layout per sample (RESULT_FLOATS = 20900 floats, a multiple of 16 bytes): verts [6890][3] | rotmat [24][9] | beta [10] | cam [3]
+// (s, tx, ty) | 1 pad float (never written).  One launch covers every sample and every replica of the launch scope (rotmat / state /
+// verts lie in the replicas' workspaces, `out` in their log blocks: rebased like every other pointer).  The vertex body moves as
+// 16-byte stores fed by 16-byte loads where the sample's vertices are 16-byte aligned (even samples: a sample's vertices start at
+// b * 20670 floats) and by two 8-byte loads otherwise; the 232-float tail (2 vertex floats, rotmat, beta, cam) goes float by float.
+#define RESULT_FLOATS 20900
+#define RESULT_BODY4 5167                   // float4 units of the vertex block (20668 of its 20670 floats)
+__global__ __launch_bounds__(256) void result_pack_kernel(const float* __restrict__ rotmat, const float* __restrict__ state,
+                                                          const float* __restrict__ verts, float* __restrict__ out, DybRep Rp) {
+  DYB_REP_PROLOGUE(Rp);
+  DYB_RB(Rp, rotmat); DYB_RB(Rp, state); DYB_RB(Rp, verts); DYB_RB(Rp, out);
+  const int b = blockIdx.y;
+  const float* v = verts + (size_t)b * NV * 3;
+  float* o = out + (size_t)b * RESULT_FLOATS;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < RESULT_BODY4) {
+    float4 x;
+    if (((uintptr_t)v & 15) == 0) {
+      x = reinterpret_cast<const float4*>(v)[i];
+    } else {
+      const float2 lo = reinterpret_cast<const float2*>(v)[2 * i], hi = reinterpret_cast<const float2*>(v)[2 * i + 1];
+      x = make_float4(lo.x, lo.y, hi.x, hi.y);
+    }
+    reinterpret_cast<float4*>(o)[i] = x;
+  } else if (i < RESULT_BODY4 + 231) {
+    const int k = i - RESULT_BODY4;            // 0, 1: the last two vertex floats | 2 .. 217 rotmat | 218 .. 227 beta | 228 .. 230 cam
+    float x;
+    if (k < 2) x = v[4 * RESULT_BODY4 + k];
+    else if (k < 218) x = rotmat[(size_t)b * 216 + (k - 2)];
+    else x = state[(size_t)b * STATE_LD + 144 + (k - 218)];       // shape at 144 .. 153, cam at 154 .. 156
+    o[4 * RESULT_BODY4 + k] = x;
+  }
+}
+// rotmat [B][24][9], state [B][160] (shape at 144, cam at 154), verts [B][6890][3] -> out [B][20900]; verts 8-byte, out 16-byte aligned
+extern "C" int dyb_result_pack(const float* rotmat, const float* state, const float* verts, float* out, int B, hipStream_t st) {
+  DYB_REQUIRE(rotmat && state && verts && out && B > 0 && B <= 64, DYB_ERR_ARG);
+  DYB_REQUIRE(((uintptr_t)verts & 7) == 0 && ((uintptr_t)out & 15) == 0, DYB_ERR_ARG);
+  const DybRep& Rp = dyb_rep_current();
+  hipLaunchKernelGGL(result_pack_kernel, dim3(dyb_cdiv(RESULT_BODY4 + 231, 256), B, Rp.n), dim3(256), 0, st, rotmat, state, verts, out, Rp);
+  DYB_CHECK_LAUNCH();
+  return DYB_OK;
+}
+
 // replica r's frame inputs (separate caller tensors) into its staging area inside the workspace, one launch for all replicas
 struct GatherArgs {
   const float* src[5][DYB_MAX_REPLICAS];     // up to five inputs per launch, per PHYSICAL replica (e.g. image, kp2d, gt_pose, gt_betas,
@@ -281,6 +325,11 @@ struct Stepper {
   const char* logs_base = nullptr;    // replica 0's block holding records | loss_log | gate_log | feat5_out (one replica arena for all four)
   size_t logs_bytes = 0;
   int record_capacity = 0, loss_capacity = 0;
+  // result ring (caller's; with replicas a fifth sub-buffer of the logs block): every final inference of a frame step is packed into
+  // row `loss_slot mod result_capacity` of each replica in that launch's scope, stream-ordered behind the inference - later steps of
+  // the frame overwrite, so what stays is each replica's own LAST inference, whichever activation arena it lived in
+  float* results = nullptr;
+  int result_capacity = 0;
   // workspace
   char* wsp = nullptr;
   bool bound = false;
@@ -356,6 +405,7 @@ struct Stepper {
     const long long* gender = nullptr;
     int slot = 0;
     bool metrics = false;
+    int loss_slot = -1;
   } tail;
   struct GtJob {
     bool on = false;
@@ -597,6 +647,7 @@ extern "C" long long dyb_stepper_get_i(const void* stepper, const char* key) {
     return (r >= 0 && r < S->nrep) ? S->adam_t_rep[r] : -1;
   }
   if (k == "drop_used") return S->drop_used;
+  if (k == "result_floats") return (long long)S->B * RESULT_FLOATS;
   if (k == "record_floats") return (long long)a64((size_t)S->B * 85 + 1);
   if (k == "loss_floats") return (S->full ? 16 : 4) * (long long)(S->inner_step + 1 + (S->full && S->dynamic ? S->optim_steps : 0));
   if (k == "slots_per_frame") return (S->eval_lower ? S->inner_step : 0) + 1 + (S->full && S->dynamic ? S->optim_steps : 0);
@@ -676,6 +727,7 @@ static int check_ready(const Stepper& S) {
     }
   }
   DYB_REQUIRE(S.inner_step >= 0 && S.inner_step <= 16 && S.n_iter >= 1 && S.n_iter <= 3, DYB_ERR_UNSUPPORTED);
+  DYB_REQUIRE(!S.results || S.result_capacity > 0, DYB_ERR_ARG);
   DYB_REQUIRE(S.kp_set == 0 || S.kp_set == 1, DYB_ERR_ARG);       // (the setter stores any value: refused here, before the first launch)
   return DYB_OK;
 }
@@ -741,12 +793,20 @@ static int record_metrics(Stepper& S, Pass& P, const long long* gender, int slot
   return DYB_OK;
 }
 
+// the final inference in pass P -> row `loss_slot mod result_capacity` of the result ring, for every replica of the current scope
+static int pack_result(Stepper& S, Pass& P, int loss_slot, hipStream_t st) {
+  if (!S.results || loss_slot < 0) return DYB_OK;
+  float* row = S.results + (size_t)(loss_slot % S.result_capacity) * S.B * RESULT_FLOATS;
+  return dyb_result_pack(P.acts + S.off_rot, P.acts + S.off_state, P.verts, row, S.B, st);
+}
+
 // issue what the side stream owes: the previous frame's final forward + record, then this frame's ground-truth meshes
 static int issue_side_work(Stepper& S, hipStream_t side) {
   if (S.tail.on) {
     HIPOK(hipStreamWaitEvent(side, S.e_theta, 0));
     RUN(pass_forward(S, S.fin, S.theta, S.tail.image, side, false));
     if (S.tail.metrics) RUN(record_metrics(S, S.fin, S.tail.gender, S.tail.slot, side));
+    RUN(pack_result(S, S.fin, S.tail.loss_slot, side));
     HIPOK(hipEventRecord(S.e_side, side));
     S.side_pending = true;
     S.tail.on = false;
@@ -1245,8 +1305,13 @@ static int make_scope(const Stepper& S, const int* idx, int n, DybRep* out) {
   arena(S.adam_m, S.n_params * sizeof(float));
   arena(S.adam_v, S.n_params * sizeof(float));
   if (S.full) arena(S.teacher, S.n_params * sizeof(float));
+  if (S.results) {
+    // the ring would be one arena too many on its own: a fifth sub-buffer of the ONE per-replica block, or refused
+    const char *r0 = reinterpret_cast<const char*>(S.results), *r1 = r0 + (size_t)(S.result_capacity > 0 ? S.result_capacity : 0) * S.B * RESULT_FLOATS * sizeof(float);
+    DYB_REQUIRE(S.logs_base && S.logs_bytes && r0 >= S.logs_base && r1 <= S.logs_base + S.logs_bytes, DYB_ERR_UNSUPPORTED);
+  }
   if (S.logs_base && S.logs_bytes) {
-    arena(S.logs_base, S.logs_bytes);              // records, loss_log, gate_log, feat5_out: sub-buffers of one per-replica block
+    arena(S.logs_base, S.logs_bytes);              // records, loss_log, gate_log, feat5_out, results: sub-buffers of one per-replica block
   } else {
     arena(S.records, (size_t)S.record_capacity * a64((size_t)S.B * 85 + 1) * sizeof(float));
     arena(S.loss_log, (size_t)S.loss_capacity * (S.full ? 16 : 4) * rows * sizeof(float));
@@ -1344,12 +1409,14 @@ static int frame_step(Stepper& S, LevelCtx& C, int record_slot, int loss_slot, i
     if (side) {
       HIPOK(hipEventRecord(S.e_theta, st));
       S.tail.on = true; S.tail.image = image; S.tail.gender = gender; S.tail.slot = slot++; S.tail.metrics = metrics;
+      S.tail.loss_slot = loss_slot;
       S.tail_stream = side;
       return DYB_OK;
     }
     RUN(pass_forward(S, S.fin, S.theta, image, st));
     RUN(settle_update(S, st));                         // (consumed by the forward above; a no-op unless that changes)
     if (metrics) RUN(record_metrics(S, S.fin, gender, slot++, st));
+    RUN(pack_result(S, S.fin, loss_slot, st));
   }
   if (!(S.full && S.dynamic)) return DYB_OK;
   // dynaboa_benchmark.py:161-192: compare features of the un-adapted and the adapted forward; while feature 12 still
@@ -1389,6 +1456,7 @@ static int frame_step(Stepper& S, LevelCtx& C, int record_slot, int loss_slot, i
       RUN(pass_forward(S, *nxt, S.theta, image, st));
       RUN(gate_cosine(S, up.acts, nxt->acts, glog + 16 * step, cos12, st));
       if (metrics) RUN(record_metrics(S, *nxt, gender, slot, st));
+      RUN(pack_result(S, *nxt, loss_slot, st));            // under the sub-scope: only the replicas still adapting overwrite their row
       post = nxt;
       S.out_in_main = (post == &S.main);
     }
@@ -1509,7 +1577,7 @@ extern "C" const float* dyb_stepper_output(const void* stepper, int which) {
   const Stepper* S = reinterpret_cast<const Stepper*>(stepper);
   if (!S || !S->bound) return nullptr;
   // (the dynamic loop's steps alternate between the two activation arenas, "share_dyn_fwd": the last launch's final inference - for a
-  // replica that left the loop a step earlier than the last one, read its prediction from the records)
+  // replica that left the loop a step earlier than the last one, read its prediction from its row of the result ring, "results")
   const Pass& F = (S->out_in_main ? S->main : S->fin);
   switch (which) {
     case 0: return F.acts + S->off_rot;

@@ -2,7 +2,7 @@
 // dyb_stepper_get_i / _f, environment variable or NULL, type I int | F double | P pointer, locked once the workspace is bound, meaning).
 // The name lookup of the setters and getters and the environment reads in dyb_stepper_create (int rows; a later set_i wins) are
 // generated from this list; defaults and the longer notes sit with the members in struct Stepper.  Keys with code of their own:
-// "adam_step", "adam_step_<replica>", "drop_seed", "drop_offset", "replicas" (locked), "logs_bytes", the "smpl_*" / "smpli_*" table
+// "adam_step", "adam_step_<replica>", "drop_seed", "drop_offset", "replicas" (locked), "logs_bytes", "result_floats" (get_i: B * 20900), the "smpl_*" / "smpli_*" table
 // families and the range check of "drop_p" (0 <= p < 1).  Measurements: DESIGN.md section 5.
 #pragma once
 #define DYB_STEPPER_OPTIONS_I(X)                                                                                                              \
@@ -33,7 +33,8 @@
   X(optim_steps, "optim_steps", nullptr, I, 0, "its iteration limit")                                                                         \
   X(kp_set, "kp_set", nullptr, I, 0, "keypoint window of the 2D term and the motion term: 0 gt24 (joints 25..48) | 1 op25 (joints 0..24)")   \
   X(record_capacity, "record_capacity", nullptr, I, 0, "metric-record slots behind `records`")                                                \
-  X(loss_capacity, "loss_capacity", nullptr, I, 0, "frames behind `loss_log` / `gate_log`")
+  X(loss_capacity, "loss_capacity", nullptr, I, 0, "frames behind `loss_log` / `gate_log`")                                                   \
+  X(result_capacity, "result_capacity", nullptr, I, 0, "rows behind `results` (a frame's final inferences go to row loss_slot mod this)")
 #define DYB_STEPPER_OPTIONS_F(X)                                                                                                              \
   X(lr, "lr", nullptr, F, 0, "Adam learning rate")                                                                                            \
   X(beta1, "beta1", nullptr, F, 0, "Adam beta1")                                                                                              \
@@ -59,13 +60,14 @@
   X(gmm_logw, "gmm_log_weights", nullptr, P, 0, "pose prior: log weights")                                                                    \
   X(j_h36m, "j_regressor_h36m", nullptr, P, 0, "[17][6890] joint regressor of the metrics")                                                   \
   X(j14, "j14", nullptr, P, 0, "[14] int: H36M -> J14 joint map")                                                                             \
-  X(logs_base, "logs_base", nullptr, P, 0, "one per-replica block holding records | loss_log | gate_log | feat5_out (with logs_bytes)")       \
+  X(logs_base, "logs_base", nullptr, P, 0, "one per-replica block holding records | loss_log | gate_log | feat5_out | results (with logs_bytes)")       \
   X(records, "records", nullptr, P, 0, "[replicas][record_capacity][record_floats]")                                                          \
   X(loss_log, "loss_log", nullptr, P, 0, "[replicas][loss_capacity][loss_floats]")                                                            \
   X(teacher, "teacher", nullptr, P, 0, "[replicas][param floats] teacher weights")                                                            \
   X(gate_host, "gate_host", nullptr, P, 0, "pinned host memory, 16 floats per replica: the gate's cosines + sequence number")                 \
   X(gate_log, "gate_log", nullptr, P, 0, "[replicas][loss_capacity][1 + optim_steps][16] cosines of every gate evaluation")                   \
   X(feat5_out, "feat5_out", nullptr, P, 0, "[replicas][B][2048] pooled feature handed to the retrieval callback")                             \
+  X(results, "results", nullptr, P, 0, "[replicas][result_capacity][result_floats] result ring: each replica's last final inference of a frame") \
   X(retrieve, "retrieve_fn", nullptr, P, 0, "int (*)(user, level, out[5]): exemplars of one sequence")                                        \
   X(retrieve_rep, "retrieve_rep_fn", nullptr, P, 0, "int (*)(user, level, physical replica, out[5]): exemplars of a replica")                 \
   X(retrieve_user, "retrieve_user", nullptr, P, 0, "first argument of the callbacks")

@@ -46,13 +46,31 @@ __device__ __forceinline__ int rnd_min(int a, int b) { return a < b ? a : b; }
 __device__ __forceinline__ int rnd_max(int a, int b) { return a > b ? a : b; }
 static inline size_t rnd_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// one mesh of a ragged call (include/dynaboa_hip.h declares the same struct)
+struct dyb_render_desc {
+  const float* verts;
+  const uint8_t* background;
+  uint8_t* out;
+  int H, W;
+};
+// mesh descriptors of a ragged call as the kernels see them (kernel arguments: no allocation, no copy, no host wait): every mesh has
+// its own vertex rows, frame and size; tile0 is the prefix of the meshes' tile counts (the flat tile grid of the ragged tile kernel)
+struct RndMesh {
+  const float* verts;
+  const uint8_t* bg;
+  uint8_t* out;
+  int H, W;
+};
+struct RndVarTab {
+  RndMesh m[RND_MAX_N];
+  int tile0[RND_MAX_N + 1];
+};
+
 // ---- vertex normals ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void render_vnormal_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                             const int* __restrict__ adj_ptr, const int* __restrict__ adj_idx, int V,
-                                                             int F, float* __restrict__ vnorm) {
-  const int v = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
-  if (v >= V) return;
-  const float* P = verts + (size_t)n * V * 3;
+// vertex v of the mesh at P -> its normal at o
+__device__ __forceinline__ void render_vnormal_body(const float* __restrict__ P, const int* __restrict__ faces,
+                                                    const int* __restrict__ adj_ptr, const int* __restrict__ adj_idx, int V, int F,
+                                                    float* __restrict__ o, int v) {
   float sx = 0.f, sy = 0.f, sz = 0.f;
   int lo = adj_ptr[v], hi = adj_ptr[v + 1];
   lo = lo < 0 ? 0 : lo;
@@ -70,10 +88,23 @@ __global__ __launch_bounds__(256) void render_vnormal_kernel(const float* __rest
   }
   const float len = sqrtf(sx * sx + sy * sy + sz * sz);
   const float inv = len > 0.f ? 1.f / len : 0.f;
-  float* o = vnorm + ((size_t)n * V + v) * 3;
   o[0] = sx * inv;
   o[1] = sy * inv;
   o[2] = sz * inv;
+}
+__global__ __launch_bounds__(256) void render_vnormal_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                             const int* __restrict__ adj_ptr, const int* __restrict__ adj_idx, int V,
+                                                             int F, float* __restrict__ vnorm) {
+  const int v = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
+  if (v >= V) return;
+  render_vnormal_body(verts + (size_t)n * V * 3, faces, adj_ptr, adj_idx, V, F, vnorm + ((size_t)n * V + v) * 3, v);
+}
+__global__ __launch_bounds__(256) void render_vnormal_var_kernel(RndVarTab tab, const int* __restrict__ faces,
+                                                                 const int* __restrict__ adj_ptr, const int* __restrict__ adj_idx,
+                                                                 int V, int F, float* __restrict__ vnorm) {
+  const int v = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
+  if (v >= V) return;
+  render_vnormal_body(tab.m[n].verts, faces, adj_ptr, adj_idx, V, F, vnorm + ((size_t)n * V + v) * 3, v);
 }
 
 // ---- face set-up ---------------------------------------------------------------------------------------------------------------
@@ -96,13 +127,10 @@ __device__ __forceinline__ long long render_edge(int ax, int ay, int bx, int by,
 // when the edge is a left edge (it runs upwards) or a top edge (horizontal, running right)
 __device__ __forceinline__ bool render_owns_edge(int ax, int ay, int bx, int by) { return by < ay || (by == ay && bx > ax); }
 
-__global__ __launch_bounds__(256) void render_face_setup_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                                const float* __restrict__ cam, int V, int F, int H, int W,
-                                                                int* __restrict__ fcoord, int* __restrict__ fbox) {
-  const int f = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
-  if (f >= F) return;
-  const float* P = verts + (size_t)n * V * 3;
-  const float sx = cam[4 * n], sy = cam[4 * n + 1], tx = cam[4 * n + 2], ty = cam[4 * n + 3];
+// face f of the mesh at P under the camera (sx, sy, tx, ty) on an H x W frame -> its snapped corners c[6] and pixel box b[2]
+__device__ __forceinline__ void render_face_setup_body(const float* __restrict__ P, const int* __restrict__ faces, float sx, float sy,
+                                                       float tx, float ty, int V, int H, int W, int* __restrict__ c,
+                                                       int* __restrict__ b, int f) {
   const float hw = 0.5f * (float)W, hh = 0.5f * (float)H;
   const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
   int x0 = 0, y0 = 0, x1 = 0, y1 = 0, x2 = 0, y2 = 0;
@@ -127,11 +155,53 @@ __global__ __launch_bounds__(256) void render_face_setup_kernel(const float* __r
       by = jlo | (jhi << 16);
     }
   }
-  const size_t g = (size_t)n * F + f;
-  int* c = fcoord + g * 6;
   c[0] = x0; c[1] = y0; c[2] = x1; c[3] = y1; c[4] = x2; c[5] = y2;
-  fbox[2 * g] = bx;
-  fbox[2 * g + 1] = by;
+  b[0] = bx;
+  b[1] = by;
+}
+__global__ __launch_bounds__(256) void render_face_setup_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                                const float* __restrict__ cam, int V, int F, int H, int W,
+                                                                int* __restrict__ fcoord, int* __restrict__ fbox) {
+  const int f = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
+  if (f >= F) return;
+  const size_t g = (size_t)n * F + f;
+  render_face_setup_body(verts + (size_t)n * V * 3, faces, cam[4 * n], cam[4 * n + 1], cam[4 * n + 2], cam[4 * n + 3], V, H, W,
+                         fcoord + g * 6, fbox + 2 * g, f);
+}
+__global__ __launch_bounds__(256) void render_face_setup_var_kernel(RndVarTab tab, const int* __restrict__ faces,
+                                                                    const float* __restrict__ cam, int V, int F,
+                                                                    int* __restrict__ fcoord, int* __restrict__ fbox) {
+  const int f = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
+  if (f >= F) return;
+  const size_t g = (size_t)n * F + f;
+  render_face_setup_body(tab.m[n].verts, faces, cam[4 * n], cam[4 * n + 1], cam[4 * n + 2], cam[4 * n + 3], V, tab.m[n].H, tab.m[n].W,
+                         fcoord + g * 6, fbox + 2 * g, f);
+}
+
+// ---- pixel box of a whole mesh (ragged entry) -----------------------------------------------------------------------------------
+// One workgroup per mesh: the union of its faces' pixel boxes, reduced in LDS with integer min / max - deterministic, no atomics.
+// mbox[4 n ..] = xlo, xhi, ylo, yhi; a mesh with no drawn face keeps the empty box (xlo > xhi).
+__global__ __launch_bounds__(256) void render_mesh_box_kernel(const int* __restrict__ fbox, int F, int* __restrict__ mbox) {
+  __shared__ int s_b[4][256];
+  const int t = threadIdx.x, n = blockIdx.x;
+  const int* B = fbox + (size_t)n * F * 2;
+  int xlo = 65535, xhi = -1, ylo = 65535, yhi = -1;
+  for (int f = t; f < F; f += 256) {
+    const int bx = B[2 * f], by = B[2 * f + 1];
+    if ((bx & 0xffff) > (bx >> 16) || (by & 0xffff) > (by >> 16)) continue;      // culled / off the frame
+    xlo = rnd_min(xlo, bx & 0xffff); xhi = rnd_max(xhi, bx >> 16);
+    ylo = rnd_min(ylo, by & 0xffff); yhi = rnd_max(yhi, by >> 16);
+  }
+  s_b[0][t] = xlo; s_b[1][t] = xhi; s_b[2][t] = ylo; s_b[3][t] = yhi;
+  __syncthreads();
+  for (int w = 128; w >= 1; w >>= 1) {
+    if (t < w) {
+      s_b[0][t] = rnd_min(s_b[0][t], s_b[0][t + w]); s_b[1][t] = rnd_max(s_b[1][t], s_b[1][t + w]);
+      s_b[2][t] = rnd_min(s_b[2][t], s_b[2][t + w]); s_b[3][t] = rnd_max(s_b[3][t], s_b[3][t + w]);
+    }
+    __syncthreads();
+  }
+  if (t < 4) mbox[4 * n + t] = s_b[t][0];
 }
 
 // ---- one workgroup per 16x16 tile ----------------------------------------------------------------------------------------------
@@ -151,39 +221,35 @@ __device__ __forceinline__ bool render_cover(int x0, int y0, int x1, int y1, int
   return (ea | eb | ec) >= 0;
 }
 
-__global__ __launch_bounds__(256) void render_tile_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                          const float* __restrict__ vnorm, const int* __restrict__ fcoord,
-                                                          const int* __restrict__ fbox, const uint8_t* __restrict__ bg, float cr,
-                                                          float cg, float cb, int V, int F, int H, int W, int wide,
-                                                          uint8_t* __restrict__ out, int* __restrict__ face_id,
-                                                          float* __restrict__ depth) {
+// The 16 x 16 tile at (tx0, ty0) of ONE mesh: P its vertex rows, N its normals, C / B its faces' snapped corners and boxes, bg / out
+// (/ face_id / depth) its own H x W images.  skip (the same for the whole workgroup): no face of the mesh touches the tile - the
+// frame is copied and the face list is not streamed.
+__device__ __forceinline__ void render_tile_body(const float* __restrict__ P, const int* __restrict__ faces, const float* __restrict__ N,
+                                                 const int* __restrict__ C, const int* __restrict__ B, const uint8_t* __restrict__ bg,
+                                                 float cr, float cg, float cb, int F, int H, int W, int wide, uint8_t* __restrict__ out,
+                                                 int* __restrict__ face_id, float* __restrict__ depth, int tx0, int ty0, bool skip) {
   __shared__ int s_xy[2][6][RND_CHUNK];
   __shared__ int s_box[2][2][RND_CHUNK];
   __shared__ float s_z[2][3][RND_CHUNK];
   __shared__ int s_f[2][RND_CHUNK];
   __shared__ unsigned s_cnt[3];
   __shared__ __attribute__((aligned(16))) uint8_t s_px[RND_TILE][RND_TILE * 3];
-  const int t = threadIdx.x, n = blockIdx.z;
-  const int tx0 = blockIdx.x * RND_TILE, ty0 = blockIdx.y * RND_TILE;
+  const int t = threadIdx.x;
   const int tx1 = rnd_min(tx0 + RND_TILE, W) - 1, ty1 = rnd_min(ty0 + RND_TILE, H) - 1;
   const int lx = t & (RND_TILE - 1), ly = t >> 4;
   const int i = tx0 + lx, j = ty0 + ly;
   const bool live = i < W && j < H;
   const int px = 256 * i + 128, py = 256 * j + 128;
-  const float* P = verts + (size_t)n * V * 3;
-  const int* C = fcoord + (size_t)n * F * 6;
-  const int* B = fbox + (size_t)n * F * 2;
-  const size_t img = (size_t)n * H * W;
   // the frame under the mesh: 16-byte rows when the layout allows it (`wide`: W a multiple of 16 and 16-byte aligned bases)
   if (wide) {
     if (t < 3 * RND_TILE) {
       const int r = t / 3, q = t - 3 * r;
       rnd_u32x4 v = {0u, 0u, 0u, 0u};
-      if (bg && ty0 + r < H) v = *reinterpret_cast<const rnd_u32x4*>(bg + (img + (size_t)(ty0 + r) * W + tx0) * 3 + 16 * q);
+      if (bg && ty0 + r < H) v = *reinterpret_cast<const rnd_u32x4*>(bg + ((size_t)(ty0 + r) * W + tx0) * 3 + 16 * q);
       *reinterpret_cast<rnd_u32x4*>(&s_px[r][16 * q]) = v;
     }
   } else {
-    const uint8_t* s = bg && live ? bg + (img + (size_t)j * W + i) * 3 : nullptr;
+    const uint8_t* s = bg && live ? bg + ((size_t)j * W + i) * 3 : nullptr;
     s_px[ly][3 * lx] = s ? s[0] : 0;
     s_px[ly][3 * lx + 1] = s ? s[1] : 0;
     s_px[ly][3 * lx + 2] = s ? s[2] : 0;
@@ -193,7 +259,7 @@ __global__ __launch_bounds__(256) void render_tile_kernel(const float* __restric
 
   float best = __uint_as_float(0x7f800000u);      // +inf
   int best_f = -1;
-  const int nchunks = (F + RND_CHUNK - 1) / RND_CHUNK;
+  const int nchunks = skip ? 0 : (F + RND_CHUNK - 1) / RND_CHUNK;
   for (int c = 0; c < nchunks; ++c) {
     const int buf = c & 1, cn = c % 3;
     // counter of the next chunk: last read two chunks ago, before the barrier every thread has passed since
@@ -243,7 +309,6 @@ __global__ __launch_bounds__(256) void render_tile_kernel(const float* __restric
     render_cover(c[0], c[1], c[2], c[3], c[4], c[5], px, py, h);
     const float ar = (float)h.area;
     const float b0 = (float)h.wa / ar, b1 = (float)h.wc / ar, b2 = (float)h.wb / ar;
-    const float* N = vnorm + (size_t)n * V * 3;
     float nx = b0 * N[3 * i0] + b1 * N[3 * i1] + b2 * N[3 * i2];
     float ny = b0 * N[3 * i0 + 1] + b1 * N[3 * i1 + 1] + b2 * N[3 * i2 + 1];
     float nz = b0 * N[3 * i0 + 2] + b1 * N[3 * i1 + 2] + b2 * N[3 * i2 + 2];
@@ -271,23 +336,63 @@ __global__ __launch_bounds__(256) void render_tile_kernel(const float* __restric
     s_px[ly][3 * lx + 2] = (uint8_t)fminf(fmaxf(rintf(255.f * I * cb), 0.f), 255.f);
   }
   if (live) {
-    if (face_id) face_id[img + (size_t)j * W + i] = best_f;
-    if (depth) depth[img + (size_t)j * W + i] = best_f >= 0 ? best : __uint_as_float(0x7f800000u);
+    if (face_id) face_id[(size_t)j * W + i] = best_f;
+    if (depth) depth[(size_t)j * W + i] = best_f >= 0 ? best : __uint_as_float(0x7f800000u);
   }
   __syncthreads();
   if (wide) {
     if (t < 3 * RND_TILE) {
       const int r = t / 3, q = t - 3 * r;
       if (ty0 + r < H)
-        *reinterpret_cast<rnd_u32x4*>(out + (img + (size_t)(ty0 + r) * W + tx0) * 3 + 16 * q) =
+        *reinterpret_cast<rnd_u32x4*>(out + ((size_t)(ty0 + r) * W + tx0) * 3 + 16 * q) =
             *reinterpret_cast<const rnd_u32x4*>(&s_px[r][16 * q]);
     }
   } else if (live) {
-    uint8_t* o = out + (img + (size_t)j * W + i) * 3;
+    uint8_t* o = out + ((size_t)j * W + i) * 3;
     o[0] = s_px[ly][3 * lx];
     o[1] = s_px[ly][3 * lx + 1];
     o[2] = s_px[ly][3 * lx + 2];
   }
+}
+
+__global__ __launch_bounds__(256) void render_tile_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                          const float* __restrict__ vnorm, const int* __restrict__ fcoord,
+                                                          const int* __restrict__ fbox, const uint8_t* __restrict__ bg, float cr,
+                                                          float cg, float cb, int V, int F, int H, int W, int wide,
+                                                          uint8_t* __restrict__ out, int* __restrict__ face_id,
+                                                          float* __restrict__ depth) {
+  const int n = blockIdx.z;
+  const size_t img = (size_t)n * H * W;
+  render_tile_body(verts + (size_t)n * V * 3, faces, vnorm + (size_t)n * V * 3, fcoord + (size_t)n * F * 6, fbox + (size_t)n * F * 2,
+                   bg ? bg + img * 3 : nullptr, cr, cg, cb, F, H, W, wide, out + img * 3, face_id ? face_id + img : nullptr,
+                   depth ? depth + img : nullptr, blockIdx.x * RND_TILE, blockIdx.y * RND_TILE, false);
+}
+// The ragged form: a flat grid over the prefix of the meshes' tile counts; workgroup -> (mesh, tile) by a search of the prefix.  A
+// tile outside its mesh's pixel box (use_box) copies the frame and leaves.
+__global__ __launch_bounds__(256) void render_tile_var_kernel(RndVarTab tab, int nmesh, const int* __restrict__ faces,
+                                                              const float* __restrict__ vnorm, const int* __restrict__ fcoord,
+                                                              const int* __restrict__ fbox, const int* __restrict__ mbox, float cr,
+                                                              float cg, float cb, int V, int F, int use_box) {
+  const int bid = (int)blockIdx.x;
+  int lo = 0, hi = nmesh;                       // the mesh n with tile0[n] <= bid < tile0[n + 1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (tab.tile0[mid] <= bid) lo = mid;
+    else hi = mid;
+  }
+  const int n = lo;
+  const RndMesh m = tab.m[n];
+  const int tw = (m.W + RND_TILE - 1) / RND_TILE, local = bid - tab.tile0[n];
+  const int ty = local / tw, tx = local - ty * tw;
+  const int tx0 = tx * RND_TILE, ty0 = ty * RND_TILE;
+  bool skip = false;
+  if (use_box) {
+    const int xlo = mbox[4 * n], xhi = mbox[4 * n + 1], ylo = mbox[4 * n + 2], yhi = mbox[4 * n + 3];
+    skip = xlo > xhi || xlo > tx0 + RND_TILE - 1 || xhi < tx0 || ylo > ty0 + RND_TILE - 1 || yhi < ty0;
+  }
+  const int wide = m.W % 16 == 0 && ((uintptr_t)m.out & 15) == 0 && ((uintptr_t)m.bg & 15) == 0;
+  render_tile_body(m.verts, faces, vnorm + (size_t)n * V * 3, fcoord + (size_t)n * F * 6, fbox + (size_t)n * F * 2, m.bg, cr, cg, cb,
+                   F, m.H, m.W, wide, m.out, nullptr, nullptr, tx0, ty0, skip);
 }
 
 // scratch: vertex normals [N][V][3] fp32 (first, so a caller can read them back), snapped corners [N][F][6] int32, boxes [N][F][2] int32
@@ -319,6 +424,57 @@ extern "C" int dyb_render_meshes(const float* verts, const int* faces, const int
   hipLaunchKernelGGL(render_tile_kernel, dim3(dyb_cdiv(W, RND_TILE), dyb_cdiv(H, RND_TILE), N), dim3(256), 0, st, verts, faces,
                      (const float*)vnorm, (const int*)fcoord, (const int*)fbox, background, col_r, col_g, col_b, V, F, H, W, wide, out,
                      face_id, depth);
+  DYB_CHECK_LAUNCH();
+  return DYB_OK;
+}
+
+// ---- the ragged entry: every mesh with its own frame size and pointers ----------------------------------------------------------
+// scratch: as above, then the meshes' pixel boxes [N][4] int32
+extern "C" size_t dyb_render_var_workspace_bytes(int N, int V, int F) {
+  if (N <= 0 || V <= 0 || F <= 0) return 0;
+  return dyb_render_workspace_bytes(N, V, F) + rnd_align((size_t)N * 4 * sizeof(int));
+}
+
+// desc: HOST table of N entries (copied into the launches' kernel arguments: free to reuse when the call returns).  flags bit 0:
+// leave the per-mesh pixel box out (every tile streams the face list, as the uniform entry does; same bytes - for measurements).
+extern "C" int dyb_render_meshes_var(const dyb_render_desc* desc, const int* faces, const int* adj_ptr, const int* adj_idx,
+                                     const float* cam, float col_r, float col_g, float col_b, int N, int V, int F, int flags, void* ws,
+                                     size_t ws_bytes, hipStream_t st) {
+  DYB_REQUIRE(desc && faces && adj_ptr && adj_idx && cam && ws, DYB_ERR_ARG);
+  DYB_REQUIRE(N > 0 && V > 0 && F > 0, DYB_ERR_ARG);
+  DYB_REQUIRE(N <= RND_MAX_N, DYB_ERR_UNSUPPORTED);
+  DYB_REQUIRE(F <= (1 << 28) && V <= (1 << 28), DYB_ERR_UNSUPPORTED);
+  RndVarTab tab{};
+  long long tiles = 0;
+  for (int n = 0; n < N; ++n) {
+    const dyb_render_desc& d = desc[n];
+    DYB_REQUIRE(d.verts && d.out && d.H > 0 && d.W > 0, DYB_ERR_ARG);
+    DYB_REQUIRE(d.H <= RND_MAX_DIM && d.W <= RND_MAX_DIM, DYB_ERR_UNSUPPORTED);
+    tab.m[n] = RndMesh{d.verts, d.background, d.out, d.H, d.W};
+    tab.tile0[n] = (int)tiles;
+    tiles += (long long)dyb_cdiv(d.W, RND_TILE) * dyb_cdiv(d.H, RND_TILE);      // <= 64 * 256 * 256: inside int and a 1-D grid
+  }
+  for (int n = N; n <= RND_MAX_N; ++n) tab.tile0[n] = (int)tiles;
+  DYB_REQUIRE(ws_bytes >= dyb_render_var_workspace_bytes(N, V, F), DYB_ERR_WORKSPACE);
+  char* w = reinterpret_cast<char*>(ws);
+  float* vnorm = reinterpret_cast<float*>(w);
+  w += rnd_align((size_t)N * V * 3 * sizeof(float));
+  int* fcoord = reinterpret_cast<int*>(w);
+  w += rnd_align((size_t)N * F * 6 * sizeof(int));
+  int* fbox = reinterpret_cast<int*>(w);
+  w += rnd_align((size_t)N * F * 2 * sizeof(int));
+  int* mbox = reinterpret_cast<int*>(w);
+  const int use_box = (flags & 1) ? 0 : 1;
+  hipLaunchKernelGGL(render_vnormal_var_kernel, dim3(dyb_cdiv(V, 256), 1, N), dim3(256), 0, st, tab, faces, adj_ptr, adj_idx, V, F, vnorm);
+  DYB_CHECK_LAUNCH();
+  hipLaunchKernelGGL(render_face_setup_var_kernel, dim3(dyb_cdiv(F, 256), 1, N), dim3(256), 0, st, tab, faces, cam, V, F, fcoord, fbox);
+  DYB_CHECK_LAUNCH();
+  if (use_box) {
+    hipLaunchKernelGGL(render_mesh_box_kernel, dim3(N), dim3(256), 0, st, (const int*)fbox, F, mbox);
+    DYB_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(render_tile_var_kernel, dim3((unsigned)tiles), dim3(256), 0, st, tab, N, faces, (const float*)vnorm,
+                     (const int*)fcoord, (const int*)fbox, (const int*)mbox, col_r, col_g, col_b, V, F, use_box);
   DYB_CHECK_LAUNCH();
   return DYB_OK;
 }

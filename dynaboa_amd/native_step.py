@@ -30,9 +30,11 @@ def coverage(o, have_bundle: bool = True):
         return "", "second order"
     if not (g("use_frame_losses_lower", 1) and g("use_frame_losses_upper", 1)):
         return "", "frame losses switched off"
-    if g("dump_predictions"):
+    # --native_results 1: the stepper keeps every frame's last final inference in its result ring (csrc/adapt_step.hip) and the
+    # adaptor writes the dump / draws the overlay from there - neither takes the run off the stepper then
+    if g("dump_predictions") and not g("native_results"):
         return "", "prediction dumps"
-    if g("save_res"):
+    if g("save_res") and not g("native_results"):
         return "", "rendered results"
     if not g("share_forwards", 1) or not g("fused_level", 1):
         return "", "unshared / unfused schedule requested"
@@ -178,15 +180,26 @@ class NativeStepper:
         n_rec, n_loss = cap * self.slots_per_frame * self.rec_floats, cap * self.loss_floats
         n_gate = cap * (1 + self.optim_steps) * 16 if self.full else 0
         n_feat = B * 2048 if self.full else 0
+        # result ring (--native_results 1 with --save_res / --dump_predictions): a fifth sub-buffer of the same block.  Two rows are
+        # enough - the host consumes a frame's row (after join()) before the frame after the next one overwrites it
+        self.result_floats = int(lib.dyb_stepper_get_i(h, b"result_floats"))
+        want_ring = bool(getattr(o, "native_results", 0)) and bool(getattr(o, "save_res", 0) or getattr(o, "dump_predictions", 0))
+        self.result_capacity = RESULT_RING_ROWS if want_ring else 0
+        n_res = self.result_capacity * self.result_floats
         pad64 = lambda n: (n + 63) // 64 * 64
         o_loss, o_gate, o_feat = pad64(n_rec), pad64(n_rec) + pad64(n_loss), pad64(n_rec) + pad64(n_loss) + pad64(n_gate)
-        self.logs = torch.zeros(S, o_feat + pad64(n_feat), device=dev)
+        o_res = o_feat + pad64(n_feat)
+        self.logs = torch.zeros(S, o_res + pad64(n_res), device=dev)
         self.records = self.logs[:, :n_rec].view(S, cap * self.slots_per_frame, self.rec_floats)
         self.loss_log = self.logs[:, o_loss:o_loss + n_loss].view(S, cap, self.loss_floats)
         sp("logs_base", self.logs)
         si("logs_bytes", self.logs.shape[1] * 4)
         si("record_capacity", cap * self.slots_per_frame); si("loss_capacity", cap)
         sp("records", self.records); sp("loss_log", self.loss_log)
+        self.results = None
+        if want_ring:
+            self.results = self.logs[:, o_res:o_res + n_res].view(S, self.result_capacity, B, self.result_floats // B)
+            sp("results", self.results); si("result_capacity", self.result_capacity)
         if self.full:
             if o.use_meanteacher:
                 if S == 1:
@@ -274,6 +287,16 @@ class NativeStepper:
         if off < 0 or off % 4 or off + 4 * n > self.ws.numel():
             raise RuntimeError("dyb_stepper_output: pointer outside the workspace")
         return self.ws[off:off + 4 * n].view(torch.float32).view(shape)
+
+    def result(self, frame: int, replica: int = 0) -> Dict[str, torch.Tensor]:
+        """Replica `replica`'s last final inference of `frame` as views of its result-ring row: vts [B][6890][3], rotmat [B][24][3][3],
+        shape [B][10], cam [B][3] = (s, tx, ty).  Valid until `result_capacity` further frames have been stepped; with a side stream
+        the row is written by the frame's owed tail - call join() first."""
+        if self.results is None:
+            raise RuntimeError("native stepper: no result ring (native_results with save_res / dump_predictions)")
+        row = self.results[replica, frame % self.result_capacity]              # [B][20900]
+        return dict(vts=row[:, :20670].unflatten(1, (6890, 3)), rotmat=row[:, 20670:20886].unflatten(1, (24, 3, 3)),
+                    shape=row[:, 20886:20896], cam=row[:, 20896:20899])
 
     def _step(self, rows, full: bool, side=None):
         """One frame step: rows[r] = replica r's input tensors in the stepper's kind order (5 kinds, or 12 with the full term set; None =
@@ -430,6 +453,9 @@ class NativeStepper:
         return c[1][r][level]
 
 
+RESULT_RING_ROWS = 2
+
+
 # Sequences per launch from which the throughput schedule (dy materialised once per layer by the one-pass GroupNorm backward, plain
 # gradient convolutions on igemm_tp_kernel) beats the latency schedule: measured crossover, frames/s latency | throughput at
 # 4: 173.6 | 169.3, 5: 185.8 | 198.9, 6: 198.4 | 222.9, 7: 206.1 | 247.9 (profiles/r05_sessions.txt s15; the library's own default
@@ -467,9 +493,12 @@ class ReplicaGroup:
         for r, a in enumerate(self.adaptors):
             a._native, a._native_replica = self.stepper, r
 
-    def step(self, batches, global_step: int):
+    def step(self, batches, global_step: int, result_steps=None):
         """One frame per sequence.  batches[r] = None: sequence r has no frame left (streams of different lengths, reference
-        boa_dataset/pw3d.py:19-35) - it sits this and all later steps out; the others are not held back by it."""
+        boa_dataset/pw3d.py:19-35) - it sits this and all later steps out; the others are not held back by it.
+        result_steps[r] (optional): the number sequence r's result files of this step carry (`Pred_{n}.png` / `.pt`) instead of
+        `global_step` - naming only (adaptors sharing one exppath: the global frame index); history / motion bookkeeping keep
+        `global_step`."""
         ns = self.stepper
         active = [r for r, b in enumerate(batches) if b is not None]
         if not active:
@@ -479,6 +508,7 @@ class ReplicaGroup:
         for r in active:
             a, b = self.adaptors[r], batches[r]
             a.global_step = global_step
+            a._result_step = None if result_steps is None else int(result_steps[r])
             a.fit_losses = {}
             a.save_hist(b["image"], b["smpl_j2d"])
         out = [None] * len(batches)
@@ -494,7 +524,24 @@ class ReplicaGroup:
             f, slot = ns.adapt_frames(full)
             for r in active:
                 out[r] = self.adaptors[r]._native_bookkeeping(f, slot)
+        if ns.results is not None:
+            self._write_results(f, active, batches)
         return out
+
+    def _write_results(self, f, active, batches):
+        """What the autograd path leaves behind for this step's frames: every sequence's prediction dump, and ALL their overlays
+        drawn by one ragged launch (dyb_render_meshes_var) straight from the ring rows."""
+        from .base_adaptor import draw_overlays
+        jobs = []
+        for r in active:
+            a, b = self.adaptors[r], batches[r]
+            res = self.stepper.result(f, r)
+            if getattr(a.options, "dump_predictions", 0):
+                a.dump_prediction(res["vts"], res["cam"], res["rotmat"], res["shape"])
+            if getattr(a.options, "save_res", 0):
+                jobs += a.overlay_jobs(res["vts"], res["cam"], b["image"], b.get("imgname"), b.get("bbox"), prefix="Pred")
+        if jobs:
+            draw_overlays(self.adaptors[active[0]].ragged_renderer(), jobs, self.adaptors[active[0]].RESULT_COLOR)
 
     def flush_metrics(self):
         from .benchmark import flush_metrics_of

@@ -7,6 +7,7 @@ term and the three light positions are the reference's; the material model is pl
 metallic-roughness one (unpinned: pyrender is absent from the build image).  Conventions: csrc/render.hip."""
 from __future__ import annotations
 
+import ctypes
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -46,6 +47,12 @@ def convert_crop_cam_to_orig_img(cam, bbox, img_width, img_height):
     scale = cam[:, :1] * bbox[:, 2:3] / frame
     shift = cam[:, 1:3] + (2.0 * bbox[:, :2] / frame - 1.0) / scale
     return cat([scale, shift], 1)
+
+
+class RenderDesc(ctypes.Structure):
+    """dyb_render_desc (include/dynaboa_hip.h): one mesh of a ragged call."""
+    _fields_ = [("verts", ctypes.c_void_p), ("background", ctypes.c_void_p), ("out", ctypes.c_void_p), ("H", ctypes.c_int),
+                ("W", ctypes.c_int)]
 
 
 class Renderer:
@@ -138,6 +145,59 @@ class Renderer:
         if as_numpy:
             res = tuple(r.cpu().numpy() for r in res)
         return res
+
+    def render_many(self, frames, verts_rows, cams, color: Sequence[float] = DEFAULT_COLOR, box: bool = True):
+        """Up to 64 meshes, each over a frame of its own size, in ONE ragged launch (dyb_render_meshes_var).  frames[i]: uint8 RGB
+        (H_i, W_i, 3) on the device or None (black - then `resolution` is the size); verts_rows[i]: (V, 3) fp32 on the device - the
+        rows may be views into different buffers (result-ring rows of different replicas); cams: (N, 4) = (sx, sy, tx, ty).
+        -> list of uint8 (H_i, W_i, 3) tensors, each equal byte for byte to ``render(frames[i], verts_rows[i], cams[i])`` on a
+        renderer of that size.  box = False leaves the per-mesh pixel box out (every tile streams the face list; same bytes)."""
+        N = len(verts_rows)
+        if N == 0:
+            return []
+        if N > MAX_MESHES or len(frames) != N:
+            raise ValueError(f"render_many draws 1 .. {MAX_MESHES} meshes, one frame (or None) each")
+        dev = verts_rows[0].device
+        c = torch.as_tensor(cams).detach().to(dev, torch.float32).reshape(N, 4).contiguous()
+        V = int(verts_rows[0].shape[0])
+        if V < self.min_verts:
+            raise ValueError(f"faces index vertex {self.min_verts - 1} but the mesh has {V} vertices")
+        lib = _lib.load()
+        faces, ptr, idx = self._adjacency(V, dev)
+        F = int(faces.shape[0])
+        desc = (RenderDesc * N)()
+        keep, outs = [], []
+        for i in range(N):
+            v = verts_rows[i].detach()
+            if v.dtype != torch.float32 or not v.is_contiguous() or v.device != dev:
+                v = v.to(dev, torch.float32).contiguous()
+            if tuple(v.shape) != (V, 3):
+                raise ValueError("verts_rows must be (V, 3) each, with one V")
+            bg = frames[i]
+            if bg is None:
+                W, H = self.resolution
+            else:
+                bg = torch.as_tensor(bg).to(dev)
+                if bg.dtype != torch.uint8 or bg.dim() != 3 or bg.shape[2] != 3:
+                    raise ValueError("the frame under the mesh must be uint8 RGB (H, W, 3)")
+                bg = bg.contiguous()
+                H, W = int(bg.shape[0]), int(bg.shape[1])
+            if not (0 < H <= MAX_DIM and 0 < W <= MAX_DIM):
+                raise ValueError(f"frame size {(H, W)} outside 1 .. {MAX_DIM}")
+            out = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+            desc[i] = RenderDesc(v.data_ptr(), bg.data_ptr() if bg is not None else None, out.data_ptr(), H, W)
+            keep += [v, bg]
+            outs.append(out)
+        nbytes = int(lib.dyb_render_var_workspace_bytes(N, V, F))
+        sid = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+        ws = self._ws.get((str(dev), sid))
+        if ws is None or ws.numel() < nbytes:
+            ws = self._ws[(str(dev), sid)] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        col = [float(x) for x in color]
+        check(lib.dyb_render_meshes_var(ctypes.cast(desc, ctypes.c_void_p), faces.data_ptr(), ptr.data_ptr(), idx.data_ptr(), c.data_ptr(),
+                                        col[0], col[1], col[2], N, V, F, 0 if box else 1, ws.data_ptr(), ws.numel(), stream_of(c)),
+              "dyb_render_meshes_var")
+        return outs
 
     def render(self, img, verts, cam, angle=None, axis=None, mesh_filename=None, color: Sequence[float] = DEFAULT_COLOR):
         """The mesh (or batch of meshes) drawn over ``img`` (uint8 RGB, (H, W, 3) or (N, H, W, 3); None = black), as uint8 of the

@@ -63,8 +63,15 @@ def run_sharded(options, sequences: Sequence[SequenceSpec], make_adaptor: Callab
         ads = [make_adaptor() for _ in wave]
         for a in ads:
             a.options.deferred_metrics = 1
+        # several sequences per GPU share one exppath: result files (--native_results 1 with --save_res / --dump_predictions) carry the
+        # GLOBAL frame index - unique, and the reference's single-stream numbering.  Naming only: history / motion keep the local step
+        number = S > 1 and bool(getattr(ads[0].options, "native_results", 0))
         if len(wave) == 1:
-            res = ads[0].excute(wave[0].frames(), nframes=steps)
+            def numbered(seq=wave[0], ad=ads[0]):
+                for k, b in enumerate(seq.frames()):
+                    ad._result_step = seq.first + k * B
+                    yield b
+            res = ads[0].excute(numbered() if number else wave[0].frames(), nframes=steps)
             per_seq = [res]
         else:
             grp = NS.ReplicaGroup(ads, steps)
@@ -77,7 +84,7 @@ def run_sharded(options, sequences: Sequence[SequenceSpec], make_adaptor: Callab
                         dev = ads[0].device
                         b = {k: v.to(dev) if isinstance(v, torch.Tensor) else v for k, v in b.items()}
                     batches.append(b)
-                grp.step(batches, step)
+                grp.step(batches, step, result_steps=[s.first + step * B for s in wave] if number else None)
             per_seq = grp.flush_metrics()
         for s, res in zip(wave, per_seq):
             mp = np.concatenate([np.ravel(np.asarray(x, np.float64)) for x in res["mpjpe"]]) if len(res["mpjpe"]) else np.zeros(0)

@@ -496,6 +496,27 @@ size_t dyb_render_workspace_bytes(int N, int V, int F);
 int dyb_render_meshes(const float* verts, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
                       const uint8_t* background, float col_r, float col_g, float col_b, uint8_t* out, int* face_id,
                       float* depth, int N, int V, int F, int H, int W, void* ws, size_t ws_bytes, dyb_stream_t stream);
+/* The ragged form: up to 64 meshes in one call, each over a frame of its own size.  desc: HOST table of N entries - verts [V][3]
+ * (device; the rows of different meshes need not be contiguous: they may point into result-ring rows of different replicas),
+ * background [H][W][3] uint8 (device) or NULL (black), out [H][W][3] uint8 (device), H, W <= 4096.  The table and the prefix of
+ * the meshes' tile counts travel as kernel arguments: no allocation, no copy, no host wait; the table may be reused when the
+ * call returns.  cam [N][4] stays a device array.  Mesh i equals, byte for byte, dyb_render_meshes called alone with that mesh,
+ * H_i, W_i (the kernels share their bodies).  One workgroup per mesh first reduces the faces' pixel boxes to the mesh's own box
+ * (integer min / max in LDS: deterministic); the tile grid is flat over all meshes and a tile outside its mesh's box copies the
+ * frame without streaming the face list (flags bit 0 set: no box, every tile streams - same bytes, for measurements; other bits 0).
+ * A mesh with no drawn face has an empty box: its picture is the frame.  DYB_ERR_ARG: NULL table / verts / out, non-positive size;
+ * DYB_ERR_UNSUPPORTED: N > 64, H or W > 4096; DYB_ERR_WORKSPACE: ws_bytes < dyb_render_var_workspace_bytes(N, V, F).  Nothing is
+ * written when an error code is returned. */
+typedef struct dyb_render_desc {
+  const float* verts;
+  const uint8_t* background;
+  uint8_t* out;
+  int H, W;
+} dyb_render_desc;
+size_t dyb_render_var_workspace_bytes(int N, int V, int F);
+int dyb_render_meshes_var(const dyb_render_desc* desc, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
+                          float col_r, float col_g, float col_b, int N, int V, int F, int flags, void* ws, size_t ws_bytes,
+                          dyb_stream_t stream);
 
 /* ---- native frame stepper: Adaptor.adaptation (reference dynaboa_benchmark.py:126-193) as ONE call per frame --------
  * The first-order bilevel schedule with the frame-loss set - clone, inner_step x [lower-level loss
@@ -510,7 +531,7 @@ int dyb_render_meshes(const float* verts, const int* faces, const int* adj_ptr, 
  * get_i / get_f return any int / double option by its key.  With code of their own:
  *   set_i: adam_step, adam_step_<replica>, replicas (1..64), logs_bytes, drop_seed, drop_offset
  *   set_p: smpl_{neutral,male,female}_{0..6} and smpli_{...}_{0..2} (the table order of dyb_lbs_fwd)
- *   get_i: adam_step, adam_step_<replica>, drop_used, slots_per_frame, record_floats (floats per metric record: pred14 [B][14][3] |
+ *   get_i: adam_step, adam_step_<replica>, drop_used, slots_per_frame, result_floats (floats per row of the result ring), record_floats (floats per metric record: pred14 [B][14][3] |
  *          gt14 [B][14][3] | mpjpe [B] | pve), loss_floats (floats per frame in loss_log: (inner_step + 1) x {s2d, shape prior, pose
  *          prior, weighted total}; full term set: 16 per level, + optim_steps levels with the dynamic loop)
  * Unknown keys are errors.
@@ -575,6 +596,19 @@ int dyb_stepper_adapt_frames_full(void* stepper, const void* const* inputs, int 
 int dyb_stepper_set_active(void* stepper, const int* idx, int n);
 int dyb_stepper_join(void* stepper, dyb_stream_t stream);
 const float* dyb_stepper_output(const void* stepper, int which);
+/* Result ring (set_p "results", set_i "result_capacity"; get_i "result_floats" = B * 20900 floats per row): with `results` set, every
+ * final inference of a frame step - the one behind the optimiser step, each step of the dynamic loop (under the scope of the
+ * replicas still adapting), the owed one on the side stream - is packed into row `loss_slot mod result_capacity` of each replica
+ * of that launch's scope, stream-ordered behind the inference it copies (no allocation, no synchronisation, no new stream; works
+ * with metrics = 0).  Later steps of the frame overwrite: what stays is each replica's own last inference, whichever activation
+ * arena it lived in; an inactive replica or one that has left the dynamic loop is not written.  results is [replicas]
+ * [result_capacity][result_floats]; with replicas > 1 it must be a FIFTH sub-buffer of the one per-replica logs block (a launch
+ * scope holds at most 8 arenas): outside it the step returns DYB_ERR_UNSUPPORTED, and results with result_capacity <= 0 is
+ * DYB_ERR_ARG, both before any launch.  Read a row after dyb_stepper_join when a side stream is in use.
+ * dyb_result_pack packs one inference into one row by one kernel: per sample verts [6890][3] | rotmat [24][9] | beta [10] | cam [3]
+ * (s, tx, ty) | 1 pad float that is never written (20900 floats, a multiple of 16 bytes).  rotmat [B][24][9], state [B][160] (shape
+ * at 144, cam at 154), verts [B][6890][3] (8-byte aligned), out [B][20900] (16-byte aligned). */
+int dyb_result_pack(const float* rotmat, const float* state, const float* verts, float* out, int B, dyb_stream_t stream);
 
 /* HMR in train() mode: nn.Dropout(p) after fc1 / fc2 of every regressor iteration (reference model/hmr.py:84,86,165,169 -
  * the reference's mean teacher runs like this, base_adaptor.py:151-158 never calls teacher.eval()).  Masks are
