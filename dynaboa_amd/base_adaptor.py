@@ -138,9 +138,13 @@ class BaseAdaptor:
             self.dataloader = self.bundle.dataloader
             return
         from . import datasets as D
-        if getattr(self.options, "dataset", "3dpw") != "3dpw":
-            raise NotImplementedError("the 'internet' demo dataset (reference boa_dataset/internet_data.py) is out of scope "
-                                      "(SURVEY 2); pass frames to excute() yourself")
+        if getattr(self.options, "dataset", "3dpw") == "internet":
+            # reference base_adaptor.py:132-134: the rows of every <internet_root>/*.npz as one stream (internet.py)
+            from . import internet as I
+            ds = I.InternetDataset(self.options, device=self.device)
+            self.imgdir = ds.img_dir
+            self.dataloader = D.FrameLoader(ds, batch_size=self.options.batch_size, workers=8) if len(ds) else None
+            return
         self.imgdir = getattr(self.options, "pw3d_root", None) or D.PW3D_ROOT
         ds = D.PW3D(self.options, img_dir=self.imgdir, device=self.device)
         self.dataloader = D.FrameLoader(ds, batch_size=self.options.batch_size, workers=8) if len(ds) else None

@@ -101,6 +101,101 @@ def preprocess_frame(img_u8: torch.Tensor, center, scale, res: int = C.IMG_RES, 
     return out
 
 
+CROP_MANY_MAX = 64            # crops per dyb_crop_resize_normalize_many call (csrc/preprocess.hip; the stepper's replica limit)
+
+
+class _CropManyRing:
+    """Staging blocks and the device workspace of ``preprocess_frames`` for one (device, stream).
+
+    The library copies a call's descriptors out of its staging block when the stream gets there, not when the call returns
+    (include/dynaboa_hip.h).  So a block that was handed to a call is not written again before the event recorded behind that call
+    has completed: the blocks form a ring, each with its event, and taking a block waits for its event.  With ``SLOTS`` calls in
+    flight that wait does not happen in practice; it is what makes reuse safe, not a synchronisation point of the path.
+    A call that fails its checks enqueues nothing: its block keeps the event of its previous use (or none) and is simply taken
+    again SLOTS calls later.  Rings are kept per raw stream handle for the life of the process; should a destroyed stream's handle
+    come back for a new stream, the ring it finds holds only events that completed long ago - waiting on them returns at once."""
+    SLOTS = 8
+
+    def __init__(self, lib, dev: torch.device):
+        self.dev, self.cuda = dev, dev.type == "cuda"
+        nbytes = int(lib.dyb_crop_many_staging_bytes(CROP_MANY_MAX))
+        self.blocks = [torch.empty(nbytes, dtype=torch.uint8, pin_memory=self.cuda) for _ in range(self.SLOTS)]
+        self.events: List[Optional[torch.cuda.Event]] = [None] * self.SLOTS
+        self.next = 0
+        self.ws = torch.empty(1 << 22, dtype=torch.uint8, device=dev)
+
+    def take(self):
+        i, self.next = self.next, (self.next + 1) % self.SLOTS
+        if self.events[i] is not None:
+            self.events[i].synchronize()
+        return i, self.blocks[i]
+
+    def done(self, i: int):
+        if self.cuda:
+            ev = self.events[i] or torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.dev))
+            self.events[i] = ev
+
+    def workspace(self, nbytes: int) -> torch.Tensor:
+        if self.ws.numel() < nbytes:
+            self.ws = torch.empty(nbytes + (nbytes >> 2), dtype=torch.uint8, device=self.dev)
+        return self.ws
+
+
+_CROP_MANY: Dict[tuple, _CropManyRing] = {}
+
+
+def preprocess_frames(frames: Sequence[torch.Tensor], centers, scales, res: int = C.IMG_RES, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``preprocess_frame`` for n crops at once: frames[i] is the uint8 (H_i, W_i, 3) device tensor crop i is cut from (the same
+    tensor may appear several times; sizes may differ) -> (n, 3, res, res) fp32, each slice bit-identical to ``preprocess_frame`` on
+    that crop.  One library call (three launches, one copy) per 64 crops; the box corners are the host arithmetic of ``crop_box``."""
+    import ctypes
+    lib = _lib.load()
+    n = len(frames)
+    if n == 0 or len(centers) != n or len(scales) != n:
+        raise ValueError("preprocess_frames expects as many centers and scales as frames, and at least one")
+    dev = frames[0].device
+    frames = [f.contiguous() for f in frames]
+    for f in frames:
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or f.device != dev:
+            raise ValueError("preprocess_frames expects uint8 (H, W, 3) RGB frames on one device")
+    boxes = np.empty((n, 4), dtype=np.int32)                    # ul_x, ul_y, br_x, br_y
+    for i in range(n):
+        ul, br = crop_box(centers[i], float(scales[i]), [res, res])
+        boxes[i] = (ul[0], ul[1], br[0], br[1])
+        if br[1] - ul[1] <= 0 or br[0] - ul[0] <= 0:
+            raise ValueError(f"empty crop box for center={centers[i]} scale={scales[i]}")
+    if out is None:
+        out = torch.empty(n, 3, res, res, dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (n, 3, res, res) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("preprocess_frames: out must be a contiguous fp32 (n, 3, res, res) tensor on the frames' device")
+    sid = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+    ring = _CROP_MANY.get((str(dev), sid))
+    if ring is None:
+        ring = _CROP_MANY[(str(dev), sid)] = _CropManyRing(lib, dev)
+    m, s = C.IMG_NORM_MEAN, C.IMG_NORM_STD
+    ip = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    for lo in range(0, n, CROP_MANY_MAX):
+        hi = min(n, lo + CROP_MANY_MAX)
+        k = hi - lo
+        imgs = np.array([f.data_ptr() for f in frames[lo:hi]], dtype=np.uint64)
+        outs = np.array([out[i].data_ptr() for i in range(lo, hi)], dtype=np.uint64)
+        hw = np.array([[f.shape[0], f.shape[1]] for f in frames[lo:hi]], dtype=np.int32)
+        H, W = np.ascontiguousarray(hw[:, 0]), np.ascontiguousarray(hw[:, 1])
+        b = boxes[lo:hi]
+        ulx, uly, brx, bry = (np.ascontiguousarray(b[:, j]) for j in range(4))
+        bh, bw = bry - uly, brx - ulx
+        ws = ring.workspace(int(lib.dyb_crop_many_workspace_bytes(k, ip(bh), ip(bw))))
+        slot, staging = ring.take()
+        check(lib.dyb_crop_resize_normalize_many(k, ip(imgs), ip(H), ip(W), ip(ulx), ip(uly), ip(brx), ip(bry), ip(outs), res,
+                                                 m[0], m[1], m[2], s[0], s[1], s[2], staging.data_ptr(), staging.numel(),
+                                                 ws.data_ptr(), ws.numel(), stream_of(frames[lo])),
+              "dyb_crop_resize_normalize_many")
+        ring.done(slot)
+    torch.autograd.graph.increment_version(out)     # as preprocess_frame: written by raw kernels
+    return out
+
+
 def key_3dpw(elem: str) -> int:
     """Ordering of the sequence files (boa_dataset/pw3d.py:19-23)."""
     elem = os.path.basename(elem)

@@ -478,6 +478,21 @@ size_t dyb_crop_workspace_bytes(int box_h, int box_w);
 int dyb_crop_resize_normalize(const uint8_t* img, int H, int W, int ul_x, int ul_y, int br_x, int br_y, float* out, int res,
                               float mean0, float mean1, float mean2, float std0, float std1, float std2, void* ws,
                               size_t ws_bytes, dyb_stream_t stream);
+/* The same for n crops in one call (1 <= n <= 64), ragged: crop i has its own frame imgs[i] of H[i] x W[i], box corners and output
+ * outs[i]; several crops may name one frame.  imgs / outs are HOST arrays of n device pointers, the int arguments HOST arrays of n.
+ * Three launches and one host-to-device copy whatever n is, no host synchronisation; every output equals, bit for bit, what
+ * dyb_crop_resize_normalize writes for that crop alone.  All crops are checked first: on an error return (n out of range, an empty
+ * box, a tap table over the limit, a short buffer) nothing has been enqueued.
+ * staging: dyb_crop_many_staging_bytes(n) bytes of host memory of the caller's (pinned, for the copy to be asynchronous).  The
+ * stream reads it AFTER the call returns: do not pass the same block to a later call, or write to it, before the stream has passed
+ * this call (an event recorded on `stream` after the call tells) - callers keep a small ring of blocks.
+ * ws: dyb_crop_many_workspace_bytes(n, box_h, box_w) bytes of device memory; calls on one stream may share it. */
+size_t dyb_crop_many_staging_bytes(int n);
+size_t dyb_crop_many_workspace_bytes(int n, const int* box_h, const int* box_w);
+int dyb_crop_resize_normalize_many(int n, const uint8_t* const* imgs, const int* H, const int* W, const int* ul_x, const int* ul_y,
+                                   const int* br_x, const int* br_y, float* const* outs, int res, float mean0, float mean1,
+                                   float mean2, float std0, float std1, float std2, void* staging, size_t staging_bytes, void* ws,
+                                   size_t ws_bytes, dyb_stream_t stream);
 
 /* ---- mesh overlay: N meshes rasterised over their frames in one call ---------------------------------------------------
  * Stands where the reference renders one frame at a time through pyrender (render_demo.py:58-134, called from
