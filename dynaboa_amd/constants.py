@@ -82,3 +82,10 @@ H36M_TO_J17 = (6, 5, 4, 1, 2, 3, 16, 15, 14, 11, 12, 13, 8, 10, 0, 7, 9)
 H36M_TO_J14 = H36M_TO_J17[:14]
 J24_TO_J17 = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 18, 14, 16, 17)
 J24_TO_J14 = J24_TO_J17[:14]
+
+# Colours of the tracked people of a scene overlay, 0 .. 255 RGB, indexed by track id modulo the length (render.track_color).
+# Entry 0 is the reference's mesh colour (base_adaptor.py:442).
+TRACK_COLORS = (
+    (205, 129, 98), (98, 160, 205), (120, 190, 110), (215, 190, 90), (165, 120, 200), (90, 195, 190), (220, 130, 165),
+    (150, 150, 160), (235, 160, 70), (110, 125, 215),
+)

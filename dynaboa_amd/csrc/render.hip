@@ -29,6 +29,9 @@
 // the faces touching the tile into LDS (with their corners and depths) and lets each thread keep the nearest face of its pixel.
 // The list is processed chunk by chunk, so no per-tile capacity can overflow (the synthetic SMPL's random-triple faces put
 // thousands of faces over one tile).
+//
+// The scene entry (end of the file) draws several meshes over ONE frame with the same bodies.  Between meshes there is no depth
+// test - each has a camera of its own, their Z are not comparable - but the painter rule: the mesh listed later is on top.
 #include "dyb_common.h"
 
 #pragma clang fp contract(off)
@@ -65,6 +68,34 @@ struct RndVarTab {
   RndMesh m[RND_MAX_N];
   int tile0[RND_MAX_N + 1];
 };
+
+// one scene of a scene call (include/dynaboa_hip.h declares the same struct): meshes [mesh_begin, mesh_end) of the call's mesh list
+// over one frame, in painter order
+struct dyb_render_scene {
+  const uint8_t* background;
+  uint8_t* out;
+  int* mesh_id;
+  int* face_id;
+  int H, W;
+  int mesh_begin, mesh_end;
+};
+// a scene call as the kernels see it, again as kernel arguments - sizes and mesh ranges packed so that 64 scenes and 64 meshes stay
+// well inside the 4 KB a launch may carry (cameras and colours are device arrays for the same reason)
+struct RndScene {
+  const uint8_t* bg;
+  uint8_t* out;
+  int* mesh_id;
+  int* face_id;
+  unsigned short H, W;                    // <= RND_MAX_DIM
+  unsigned char m0, m1;                   // meshes [m0, m1) of the list, <= RND_MAX_N
+};
+struct RndSceneTab {
+  RndScene s[RND_MAX_N];
+  const float* verts[RND_MAX_N];          // per mesh
+  int tile0[RND_MAX_N + 1];               // prefix of the scenes' tile counts
+  unsigned char scene_of[RND_MAX_N];      // per mesh
+};
+static_assert(sizeof(RndSceneTab) <= 3584, "the scene table and the other arguments of a launch must fit in 4 KB");
 
 // ---- vertex normals ------------------------------------------------------------------------------------------------------------
 // vertex v of the mesh at P -> its normal at o
@@ -105,6 +136,14 @@ __global__ __launch_bounds__(256) void render_vnormal_var_kernel(RndVarTab tab, 
   const int v = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
   if (v >= V) return;
   render_vnormal_body(tab.m[n].verts, faces, adj_ptr, adj_idx, V, F, vnorm + ((size_t)n * V + v) * 3, v);
+}
+
+__global__ __launch_bounds__(256) void render_vnormal_scene_kernel(RndSceneTab tab, const int* __restrict__ faces,
+                                                                   const int* __restrict__ adj_ptr, const int* __restrict__ adj_idx,
+                                                                   int V, int F, float* __restrict__ vnorm) {
+  const int v = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
+  if (v >= V) return;
+  render_vnormal_body(tab.verts[n], faces, adj_ptr, adj_idx, V, F, vnorm + ((size_t)n * V + v) * 3, v);
 }
 
 // ---- face set-up ---------------------------------------------------------------------------------------------------------------
@@ -178,6 +217,18 @@ __global__ __launch_bounds__(256) void render_face_setup_var_kernel(RndVarTab ta
                          fcoord + g * 6, fbox + 2 * g, f);
 }
 
+// a mesh of a scene call is set up on its scene's frame size
+__global__ __launch_bounds__(256) void render_face_setup_scene_kernel(RndSceneTab tab, const int* __restrict__ faces,
+                                                                      const float* __restrict__ cam, int V, int F,
+                                                                      int* __restrict__ fcoord, int* __restrict__ fbox) {
+  const int f = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
+  if (f >= F) return;
+  const size_t g = (size_t)n * F + f;
+  const int k = tab.scene_of[n];
+  render_face_setup_body(tab.verts[n], faces, cam[4 * n], cam[4 * n + 1], cam[4 * n + 2], cam[4 * n + 3], V, tab.s[k].H, tab.s[k].W,
+                         fcoord + g * 6, fbox + 2 * g, f);
+}
+
 // ---- pixel box of a whole mesh (ragged entry) -----------------------------------------------------------------------------------
 // One workgroup per mesh: the union of its faces' pixel boxes, reduced in LDS with integer min / max - deterministic, no atomics.
 // mbox[4 n ..] = xlo, xhi, ylo, yhi; a mesh with no drawn face keeps the empty box (xlo > xhi).
@@ -221,6 +272,130 @@ __device__ __forceinline__ bool render_cover(int x0, int y0, int x1, int y1, int
   return (ea | eb | ec) >= 0;
 }
 
+// The frame under a tile -> the tile's LDS picture s_px, and back: 16-byte rows when the layout allows it (`wide`: W a multiple of 16
+// and 16-byte aligned bases), else one pixel per thread.  bg NULL: black.  The callers put a barrier between either of them and
+// any other use of s_px.
+__device__ __forceinline__ void render_frame_load(uint8_t (*s_px)[RND_TILE * 3], const uint8_t* __restrict__ bg, int H, int W, int wide,
+                                                  int tx0, int ty0, int t, int lx, int ly, int i, int j, bool live) {
+  if (wide) {
+    if (t < 3 * RND_TILE) {
+      const int r = t / 3, q = t - 3 * r;
+      rnd_u32x4 v = {0u, 0u, 0u, 0u};
+      if (bg && ty0 + r < H) v = *reinterpret_cast<const rnd_u32x4*>(bg + ((size_t)(ty0 + r) * W + tx0) * 3 + 16 * q);
+      *reinterpret_cast<rnd_u32x4*>(&s_px[r][16 * q]) = v;
+    }
+  } else {
+    const uint8_t* s = bg && live ? bg + ((size_t)j * W + i) * 3 : nullptr;
+    s_px[ly][3 * lx] = s ? s[0] : 0;
+    s_px[ly][3 * lx + 1] = s ? s[1] : 0;
+    s_px[ly][3 * lx + 2] = s ? s[2] : 0;
+  }
+}
+__device__ __forceinline__ void render_frame_store(uint8_t (*s_px)[RND_TILE * 3], uint8_t* __restrict__ out, int H, int W, int wide,
+                                                   int tx0, int ty0, int t, int lx, int ly, int i, int j, bool live) {
+  if (wide) {
+    if (t < 3 * RND_TILE) {
+      const int r = t / 3, q = t - 3 * r;
+      if (ty0 + r < H)
+        *reinterpret_cast<rnd_u32x4*>(out + ((size_t)(ty0 + r) * W + tx0) * 3 + 16 * q) =
+            *reinterpret_cast<const rnd_u32x4*>(&s_px[r][16 * q]);
+    }
+  } else if (live) {
+    uint8_t* o = out + ((size_t)j * W + i) * 3;
+    o[0] = s_px[ly][3 * lx];
+    o[1] = s_px[ly][3 * lx + 1];
+    o[2] = s_px[ly][3 * lx + 2];
+  }
+}
+// The colour of the pixel centre (px, py) where face f of the mesh (P, N its vertex rows and normals, C its snapped corners) won:
+// smooth shading as the header states it -> rgb[3].  The one statement of that arithmetic: every tile kernel shades through it.
+__device__ __forceinline__ void render_shade(const float* __restrict__ P, const int* __restrict__ faces, const float* __restrict__ N,
+                                             const int* __restrict__ C, int f, int px, int py, float cr, float cg, float cb,
+                                             uint8_t* rgb) {
+  const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+  const int* c = C + 6 * (size_t)f;
+  RenderHit h;
+  render_cover(c[0], c[1], c[2], c[3], c[4], c[5], px, py, h);
+  const float ar = (float)h.area;
+  const float b0 = (float)h.wa / ar, b1 = (float)h.wc / ar, b2 = (float)h.wb / ar;
+  float nx = b0 * N[3 * i0] + b1 * N[3 * i1] + b2 * N[3 * i2];
+  float ny = b0 * N[3 * i0 + 1] + b1 * N[3 * i1 + 1] + b2 * N[3 * i2 + 1];
+  float nz = b0 * N[3 * i0 + 2] + b1 * N[3 * i1 + 2] + b2 * N[3 * i2 + 2];
+  const float nl = sqrtf(nx * nx + ny * ny + nz * nz);
+  const float ni = nl > 0.f ? 1.f / nl : 0.f;
+  // the turned space: (x, -y, -z) for positions and normals alike
+  nx = nx * ni;
+  ny = -(ny * ni);
+  nz = -(nz * ni);
+  const float qx = b0 * P[3 * i0] + b1 * P[3 * i1] + b2 * P[3 * i2];
+  const float qy = -(b0 * P[3 * i0 + 1] + b1 * P[3 * i1 + 1] + b2 * P[3 * i2 + 1]);
+  const float qz = -(b0 * P[3 * i0 + 2] + b1 * P[3 * i1 + 2] + b2 * P[3 * i2 + 2]);
+  const float L[3][3] = {{0.f, -1.f, 1.f}, {0.f, 1.f, 1.f}, {1.f, 1.f, 2.f}};
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float dx = L[k][0] - qx, dy = L[k][1] - qy, dz = L[k][2] - qz;
+    const float dl = sqrtf(dx * dx + dy * dy + dz * dz);
+    const float dot = dl > 0.f ? (nx * dx + ny * dy + nz * dz) / dl : 0.f;
+    sum += fmaxf(dot, 0.f);
+  }
+  const float I = fminf(0.3f + 0.35f * sum, 1.f);
+  rgb[0] = (uint8_t)fminf(fmaxf(rintf(255.f * I * cr), 0.f), 255.f);
+  rgb[1] = (uint8_t)fminf(fmaxf(rintf(255.f * I * cg), 0.f), 255.f);
+  rgb[2] = (uint8_t)fminf(fmaxf(rintf(255.f * I * cb), 0.f), 255.f);
+}
+
+// One chunk of a mesh's face list over the tile (tx0 .. tx1, ty0 .. ty1): faces c * 256 .. of the mesh (P, C, B as in the tile body)
+// whose box touches the tile are compacted into LDS with their corners and depths, and a pixel that takes part (`test`) keeps the
+// nearest face covering it in (best, best_f); ties go to the lower face index.  g: the running number of the chunk in this workgroup
+// - the LDS entries are double-buffered and the counters rotate by it (g = c for one mesh; a workgroup that walks several meshes
+// goes on counting).  Every thread of the workgroup calls it: it holds a barrier.
+__device__ __forceinline__ void render_chunk_nearest(const float* __restrict__ P, const int* __restrict__ faces, const int* __restrict__ C,
+                                                     const int* __restrict__ B, int F, int c, int g, int tx0, int tx1, int ty0, int ty1,
+                                                     int t, int i, int j, int px, int py, bool test, int (*s_xy)[6][RND_CHUNK],
+                                                     int (*s_box)[2][RND_CHUNK], float (*s_z)[3][RND_CHUNK], int (*s_f)[RND_CHUNK],
+                                                     unsigned* s_cnt, float& best, int& best_f) {
+  const int buf = g & 1, cn = g % 3;
+  // counter of the next chunk: last read two chunks ago, before the barrier every thread has passed since
+  if (t == 0) s_cnt[(g + 1) % 3] = 0;
+  const int f = c * RND_CHUNK + t;
+  if (f < F) {
+    const int bx = B[2 * f], by = B[2 * f + 1];
+    if ((bx & 0xffff) <= tx1 && (bx >> 16) >= tx0 && (by & 0xffff) <= ty1 && (by >> 16) >= ty0) {
+      const unsigned s = atomicAdd(&s_cnt[cn], 1u);
+      const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];      // in range: set-up gave a box
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s_xy[buf][k][s] = C[6 * (size_t)f + k];
+      s_box[buf][0][s] = bx;
+      s_box[buf][1][s] = by;
+      s_z[buf][0][s] = P[3 * i0 + 2];
+      s_z[buf][1][s] = P[3 * i1 + 2];
+      s_z[buf][2][s] = P[3 * i2 + 2];
+      s_f[buf][s] = f;
+    }
+  }
+  __syncthreads();
+  const int m = (int)s_cnt[cn];
+  if (test) {
+    for (int e = 0; e < m; ++e) {
+      const int bx = s_box[buf][0][e], by = s_box[buf][1][e];
+      if (i < (bx & 0xffff) || i > (bx >> 16) || j < (by & 0xffff) || j > (by >> 16)) continue;
+      RenderHit h;
+      if (!render_cover(s_xy[buf][0][e], s_xy[buf][1][e], s_xy[buf][2][e], s_xy[buf][3][e], s_xy[buf][4][e], s_xy[buf][5][e], px,
+                        py, h))
+        continue;
+      // weights of v0, v1, v2 = wa, wc, wb
+      const float d = ((float)h.wa * s_z[buf][0][e] + (float)h.wc * s_z[buf][1][e] + (float)h.wb * s_z[buf][2][e]) / (float)h.area;
+      const int f2 = s_f[buf][e];
+      if (d < best || (d == best && f2 < best_f) || best_f < 0) {
+        best = d;
+        best_f = f2;
+      }
+    }
+  }
+  // the entries of this chunk are overwritten two chunks on, behind the next barrier
+}
+
 // The 16 x 16 tile at (tx0, ty0) of ONE mesh: P its vertex rows, N its normals, C / B its faces' snapped corners and boxes, bg / out
 // (/ face_id / depth) its own H x W images.  skip (the same for the whole workgroup): no face of the mesh touches the tile - the
 // frame is copied and the face list is not streamed.
@@ -240,20 +415,7 @@ __device__ __forceinline__ void render_tile_body(const float* __restrict__ P, co
   const int i = tx0 + lx, j = ty0 + ly;
   const bool live = i < W && j < H;
   const int px = 256 * i + 128, py = 256 * j + 128;
-  // the frame under the mesh: 16-byte rows when the layout allows it (`wide`: W a multiple of 16 and 16-byte aligned bases)
-  if (wide) {
-    if (t < 3 * RND_TILE) {
-      const int r = t / 3, q = t - 3 * r;
-      rnd_u32x4 v = {0u, 0u, 0u, 0u};
-      if (bg && ty0 + r < H) v = *reinterpret_cast<const rnd_u32x4*>(bg + ((size_t)(ty0 + r) * W + tx0) * 3 + 16 * q);
-      *reinterpret_cast<rnd_u32x4*>(&s_px[r][16 * q]) = v;
-    }
-  } else {
-    const uint8_t* s = bg && live ? bg + ((size_t)j * W + i) * 3 : nullptr;
-    s_px[ly][3 * lx] = s ? s[0] : 0;
-    s_px[ly][3 * lx + 1] = s ? s[1] : 0;
-    s_px[ly][3 * lx + 2] = s ? s[2] : 0;
-  }
+  render_frame_load(s_px, bg, H, W, wide, tx0, ty0, t, lx, ly, i, j, live);
   if (t < 3) s_cnt[t] = 0;
   __syncthreads();
 
@@ -261,98 +423,16 @@ __device__ __forceinline__ void render_tile_body(const float* __restrict__ P, co
   int best_f = -1;
   const int nchunks = skip ? 0 : (F + RND_CHUNK - 1) / RND_CHUNK;
   for (int c = 0; c < nchunks; ++c) {
-    const int buf = c & 1, cn = c % 3;
-    // counter of the next chunk: last read two chunks ago, before the barrier every thread has passed since
-    if (t == 0) s_cnt[(c + 1) % 3] = 0;
-    const int f = c * RND_CHUNK + t;
-    if (f < F) {
-      const int bx = B[2 * f], by = B[2 * f + 1];
-      if ((bx & 0xffff) <= tx1 && (bx >> 16) >= tx0 && (by & 0xffff) <= ty1 && (by >> 16) >= ty0) {
-        const unsigned s = atomicAdd(&s_cnt[cn], 1u);
-        const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];      // in range: set-up gave a box
-#pragma unroll
-        for (int k = 0; k < 6; ++k) s_xy[buf][k][s] = C[6 * (size_t)f + k];
-        s_box[buf][0][s] = bx;
-        s_box[buf][1][s] = by;
-        s_z[buf][0][s] = P[3 * i0 + 2];
-        s_z[buf][1][s] = P[3 * i1 + 2];
-        s_z[buf][2][s] = P[3 * i2 + 2];
-        s_f[buf][s] = f;
-      }
-    }
-    __syncthreads();
-    const int m = (int)s_cnt[cn];
-    if (live) {
-      for (int e = 0; e < m; ++e) {
-        const int bx = s_box[buf][0][e], by = s_box[buf][1][e];
-        if (i < (bx & 0xffff) || i > (bx >> 16) || j < (by & 0xffff) || j > (by >> 16)) continue;
-        RenderHit h;
-        if (!render_cover(s_xy[buf][0][e], s_xy[buf][1][e], s_xy[buf][2][e], s_xy[buf][3][e], s_xy[buf][4][e], s_xy[buf][5][e], px,
-                          py, h))
-          continue;
-        // weights of v0, v1, v2 = wa, wc, wb
-        const float d = ((float)h.wa * s_z[buf][0][e] + (float)h.wc * s_z[buf][1][e] + (float)h.wb * s_z[buf][2][e]) / (float)h.area;
-        const int f2 = s_f[buf][e];
-        if (d < best || (d == best && f2 < best_f) || best_f < 0) {
-          best = d;
-          best_f = f2;
-        }
-      }
-    }
-    // the entries of this chunk are overwritten two chunks on, behind the next barrier
+    render_chunk_nearest(P, faces, C, B, F, c, c, tx0, tx1, ty0, ty1, t, i, j, px, py, live, s_xy, s_box, s_z, s_f, s_cnt, best, best_f);
   }
 
-  if (live && best_f >= 0) {
-    const int i0 = faces[3 * best_f], i1 = faces[3 * best_f + 1], i2 = faces[3 * best_f + 2];
-    const int* c = C + 6 * (size_t)best_f;
-    RenderHit h;
-    render_cover(c[0], c[1], c[2], c[3], c[4], c[5], px, py, h);
-    const float ar = (float)h.area;
-    const float b0 = (float)h.wa / ar, b1 = (float)h.wc / ar, b2 = (float)h.wb / ar;
-    float nx = b0 * N[3 * i0] + b1 * N[3 * i1] + b2 * N[3 * i2];
-    float ny = b0 * N[3 * i0 + 1] + b1 * N[3 * i1 + 1] + b2 * N[3 * i2 + 1];
-    float nz = b0 * N[3 * i0 + 2] + b1 * N[3 * i1 + 2] + b2 * N[3 * i2 + 2];
-    const float nl = sqrtf(nx * nx + ny * ny + nz * nz);
-    const float ni = nl > 0.f ? 1.f / nl : 0.f;
-    // the turned space: (x, -y, -z) for positions and normals alike
-    nx = nx * ni;
-    ny = -(ny * ni);
-    nz = -(nz * ni);
-    const float qx = b0 * P[3 * i0] + b1 * P[3 * i1] + b2 * P[3 * i2];
-    const float qy = -(b0 * P[3 * i0 + 1] + b1 * P[3 * i1 + 1] + b2 * P[3 * i2 + 1]);
-    const float qz = -(b0 * P[3 * i0 + 2] + b1 * P[3 * i1 + 2] + b2 * P[3 * i2 + 2]);
-    const float L[3][3] = {{0.f, -1.f, 1.f}, {0.f, 1.f, 1.f}, {1.f, 1.f, 2.f}};
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float dx = L[k][0] - qx, dy = L[k][1] - qy, dz = L[k][2] - qz;
-      const float dl = sqrtf(dx * dx + dy * dy + dz * dz);
-      const float dot = dl > 0.f ? (nx * dx + ny * dy + nz * dz) / dl : 0.f;
-      sum += fmaxf(dot, 0.f);
-    }
-    const float I = fminf(0.3f + 0.35f * sum, 1.f);
-    s_px[ly][3 * lx] = (uint8_t)fminf(fmaxf(rintf(255.f * I * cr), 0.f), 255.f);
-    s_px[ly][3 * lx + 1] = (uint8_t)fminf(fmaxf(rintf(255.f * I * cg), 0.f), 255.f);
-    s_px[ly][3 * lx + 2] = (uint8_t)fminf(fmaxf(rintf(255.f * I * cb), 0.f), 255.f);
-  }
+  if (live && best_f >= 0) render_shade(P, faces, N, C, best_f, px, py, cr, cg, cb, &s_px[ly][3 * lx]);
   if (live) {
     if (face_id) face_id[(size_t)j * W + i] = best_f;
     if (depth) depth[(size_t)j * W + i] = best_f >= 0 ? best : __uint_as_float(0x7f800000u);
   }
   __syncthreads();
-  if (wide) {
-    if (t < 3 * RND_TILE) {
-      const int r = t / 3, q = t - 3 * r;
-      if (ty0 + r < H)
-        *reinterpret_cast<rnd_u32x4*>(out + ((size_t)(ty0 + r) * W + tx0) * 3 + 16 * q) =
-            *reinterpret_cast<const rnd_u32x4*>(&s_px[r][16 * q]);
-    }
-  } else if (live) {
-    uint8_t* o = out + ((size_t)j * W + i) * 3;
-    o[0] = s_px[ly][3 * lx];
-    o[1] = s_px[ly][3 * lx + 1];
-    o[2] = s_px[ly][3 * lx + 2];
-  }
+  render_frame_store(s_px, out, H, W, wide, tx0, ty0, t, lx, ly, i, j, live);
 }
 
 __global__ __launch_bounds__(256) void render_tile_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
@@ -475,6 +555,152 @@ extern "C" int dyb_render_meshes_var(const dyb_render_desc* desc, const int* fac
   }
   hipLaunchKernelGGL(render_tile_var_kernel, dim3((unsigned)tiles), dim3(256), 0, st, tab, N, faces, (const float*)vnorm,
                      (const int*)fcoord, (const int*)fbox, (const int*)mbox, col_r, col_g, col_b, V, F, use_box);
+  DYB_CHECK_LAUNCH();
+  return DYB_OK;
+}
+
+// ---- the scene entry: several meshes over ONE frame, in painter order ------------------------------------------------------------
+// Each mesh of a scene has its own weak-perspective camera: the Z of two people is measured about two pelvises and cannot be
+// compared, so there is NO depth test between meshes.  Within a mesh the nearest face wins (ties: the lower index), between meshes
+// the one listed later wins wherever it covers the pixel - what the chain  img = render(img, mesh_i)  over the list draws, byte for
+// byte.  One workgroup per tile of a scene walks the scene's meshes from the last (on top) to the first: a pixel is decided by the
+// first mesh it meets that covers it, a decided pixel makes no more coverage tests, and the walk ends when every live pixel of the
+// tile is decided.  The pixel is shaded once, at the end, with the winner's vertex rows, normals and colour.
+__global__ __launch_bounds__(256) void render_tile_scene_kernel(RndSceneTab tab, int nscenes, const int* __restrict__ faces,
+                                                                const float* __restrict__ vnorm, const int* __restrict__ fcoord,
+                                                                const int* __restrict__ fbox, const int* __restrict__ mbox,
+                                                                const float* __restrict__ colors, int V, int F, int use_box) {
+  __shared__ int s_xy[2][6][RND_CHUNK];
+  __shared__ int s_box[2][2][RND_CHUNK];
+  __shared__ float s_z[2][3][RND_CHUNK];
+  __shared__ int s_f[2][RND_CHUNK];
+  __shared__ unsigned s_cnt[3];
+  __shared__ unsigned s_decided;
+  __shared__ __attribute__((aligned(16))) uint8_t s_px[RND_TILE][RND_TILE * 3];
+  const int bid = (int)blockIdx.x;
+  int lo = 0, hi = nscenes;                     // the scene k with tile0[k] <= bid < tile0[k + 1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (tab.tile0[mid] <= bid) lo = mid;
+    else hi = mid;
+  }
+  const RndScene sc = tab.s[lo];
+  const int H = sc.H, W = sc.W;
+  const int tw = (W + RND_TILE - 1) / RND_TILE, local = bid - tab.tile0[lo];
+  const int tyi = local / tw, txi = local - tyi * tw;
+  const int tx0 = txi * RND_TILE, ty0 = tyi * RND_TILE;
+  const int wide = W % 16 == 0 && ((uintptr_t)sc.out & 15) == 0 && ((uintptr_t)sc.bg & 15) == 0;
+  const int t = threadIdx.x;
+  const int tx1 = rnd_min(tx0 + RND_TILE, W) - 1, ty1 = rnd_min(ty0 + RND_TILE, H) - 1;
+  const int lx = t & (RND_TILE - 1), ly = t >> 4;
+  const int i = tx0 + lx, j = ty0 + ly;
+  const bool live = i < W && j < H;
+  const int px = 256 * i + 128, py = 256 * j + 128;
+  const unsigned nlive = (unsigned)((tx1 - tx0 + 1) * (ty1 - ty0 + 1));
+  render_frame_load(s_px, sc.bg, H, W, wide, tx0, ty0, t, lx, ly, i, j, live);
+  if (t < 3) s_cnt[t] = 0;
+  if (t == 0) s_decided = 0;
+  __syncthreads();
+
+  int win_m = -1, win_f = -1;                   // the mesh (index in the call's list) and the face this pixel shows
+  const int nchunks = (F + RND_CHUNK - 1) / RND_CHUNK;
+  int g = 0;                                    // chunks streamed so far, over all meshes
+  for (int m = (int)sc.m1 - 1; m >= (int)sc.m0; --m) {
+    if (use_box) {                              // the same for the whole workgroup
+      const int xlo = mbox[4 * m], xhi = mbox[4 * m + 1], ylo = mbox[4 * m + 2], yhi = mbox[4 * m + 3];
+      if (xlo > xhi || xlo > tx1 || xhi < tx0 || ylo > ty1 || yhi < ty0) continue;
+    }
+    const float* P = tab.verts[m];
+    const int* C = fcoord + (size_t)m * F * 6;
+    const int* B = fbox + (size_t)m * F * 2;
+    float best = __uint_as_float(0x7f800000u);
+    int best_f = -1;
+    // a decided pixel tests nothing, but goes through the barriers with the others
+    for (int c = 0; c < nchunks; ++c, ++g)
+      render_chunk_nearest(P, faces, C, B, F, c, g, tx0, tx1, ty0, ty1, t, i, j, px, py, live && win_m < 0, s_xy, s_box, s_z, s_f, s_cnt,
+                           best, best_f);
+    if (live && win_m < 0 && best_f >= 0) {
+      win_m = m;
+      win_f = best_f;
+      atomicAdd(&s_decided, 1u);
+    }
+    // read behind the barrier: one value for the whole workgroup.  The next addition to it lies behind a barrier of the next mesh's
+    // first chunk, which no thread passes before all have read it here.
+    __syncthreads();
+    if (s_decided == nlive) break;
+  }
+
+  if (live && win_m >= 0)
+    render_shade(tab.verts[win_m], faces, vnorm + (size_t)win_m * V * 3, fcoord + (size_t)win_m * F * 6, win_f, px, py,
+                 colors[3 * win_m], colors[3 * win_m + 1], colors[3 * win_m + 2], &s_px[ly][3 * lx]);
+  if (live) {
+    if (sc.mesh_id) sc.mesh_id[(size_t)j * W + i] = win_m >= 0 ? win_m - (int)sc.m0 : -1;
+    if (sc.face_id) sc.face_id[(size_t)j * W + i] = win_f;
+  }
+  __syncthreads();
+  render_frame_store(s_px, sc.out, H, W, wide, tx0, ty0, t, lx, ly, i, j, live);
+}
+
+// scratch: that of the ragged entry for nmeshes meshes (normals, snapped corners, face boxes, mesh boxes); none without a mesh
+extern "C" size_t dyb_render_scenes_workspace_bytes(int nmeshes, int V, int F) { return dyb_render_var_workspace_bytes(nmeshes, V, F); }
+
+// scenes: HOST table of nscenes entries; mesh_verts: HOST table of nmeshes device pointers; mesh_scene: HOST table, the scene of
+// each mesh (it must agree with the scenes' ranges, which must tile 0 .. nmeshes in order).  Both are copied into the launches'
+// kernel arguments.  flags bit 0: leave the per-mesh pixel boxes out (same bytes - for measurements).
+extern "C" int dyb_render_scenes(const dyb_render_scene* scenes, int nscenes, const float* const* mesh_verts, const int* mesh_scene,
+                                 const float* cam, const float* colors, const int* faces, const int* adj_ptr, const int* adj_idx,
+                                 int nmeshes, int V, int F, int flags, void* ws, size_t ws_bytes, hipStream_t st) {
+  DYB_REQUIRE(scenes && faces && adj_ptr && adj_idx, DYB_ERR_ARG);
+  DYB_REQUIRE(nscenes > 0 && nmeshes >= 0 && V > 0 && F > 0, DYB_ERR_ARG);
+  DYB_REQUIRE(nmeshes == 0 || (mesh_verts && mesh_scene && cam && colors && ws), DYB_ERR_ARG);
+  DYB_REQUIRE(nscenes <= RND_MAX_N && nmeshes <= RND_MAX_N, DYB_ERR_UNSUPPORTED);
+  DYB_REQUIRE(F <= (1 << 28) && V <= (1 << 28), DYB_ERR_UNSUPPORTED);
+  RndSceneTab tab{};
+  long long tiles = 0;
+  int next = 0;
+  for (int k = 0; k < nscenes; ++k) {
+    const dyb_render_scene& d = scenes[k];
+    DYB_REQUIRE(d.out && d.H > 0 && d.W > 0, DYB_ERR_ARG);
+    DYB_REQUIRE(d.mesh_begin == next && d.mesh_end >= d.mesh_begin && d.mesh_end <= nmeshes, DYB_ERR_ARG);
+    DYB_REQUIRE(d.H <= RND_MAX_DIM && d.W <= RND_MAX_DIM, DYB_ERR_UNSUPPORTED);
+    next = d.mesh_end;
+    tab.s[k] = RndScene{d.background, d.out, d.mesh_id, d.face_id, (unsigned short)d.H, (unsigned short)d.W,
+                        (unsigned char)d.mesh_begin, (unsigned char)d.mesh_end};
+    for (int m = d.mesh_begin; m < d.mesh_end; ++m) {
+      DYB_REQUIRE(mesh_verts[m] && mesh_scene[m] == k, DYB_ERR_ARG);
+      tab.verts[m] = mesh_verts[m];
+      tab.scene_of[m] = (unsigned char)k;
+    }
+    tab.tile0[k] = (int)tiles;
+    tiles += (long long)dyb_cdiv(d.W, RND_TILE) * dyb_cdiv(d.H, RND_TILE);      // <= 64 * 256 * 256: inside int and a 1-D grid
+  }
+  DYB_REQUIRE(next == nmeshes, DYB_ERR_ARG);
+  for (int k = nscenes; k <= RND_MAX_N; ++k) tab.tile0[k] = (int)tiles;
+  DYB_REQUIRE(ws_bytes >= dyb_render_scenes_workspace_bytes(nmeshes, V, F), DYB_ERR_WORKSPACE);
+  const int M = nmeshes;
+  char* w = reinterpret_cast<char*>(ws);
+  float* vnorm = reinterpret_cast<float*>(w);
+  w += rnd_align((size_t)M * V * 3 * sizeof(float));
+  int* fcoord = reinterpret_cast<int*>(w);
+  w += rnd_align((size_t)M * F * 6 * sizeof(int));
+  int* fbox = reinterpret_cast<int*>(w);
+  w += rnd_align((size_t)M * F * 2 * sizeof(int));
+  int* mbox = reinterpret_cast<int*>(w);
+  const int use_box = (flags & 1) ? 0 : 1;
+  if (M > 0) {
+    hipLaunchKernelGGL(render_vnormal_scene_kernel, dim3(dyb_cdiv(V, 256), 1, M), dim3(256), 0, st, tab, faces, adj_ptr, adj_idx, V, F,
+                       vnorm);
+    DYB_CHECK_LAUNCH();
+    hipLaunchKernelGGL(render_face_setup_scene_kernel, dim3(dyb_cdiv(F, 256), 1, M), dim3(256), 0, st, tab, faces, cam, V, F, fcoord,
+                       fbox);
+    DYB_CHECK_LAUNCH();
+    if (use_box) {
+      hipLaunchKernelGGL(render_mesh_box_kernel, dim3(M), dim3(256), 0, st, (const int*)fbox, F, mbox);
+      DYB_CHECK_LAUNCH();
+    }
+  }
+  hipLaunchKernelGGL(render_tile_scene_kernel, dim3((unsigned)tiles), dim3(256), 0, st, tab, nscenes, faces, (const float*)vnorm,
+                     (const int*)fcoord, (const int*)fbox, (const int*)mbox, colors, V, F, use_box);
   DYB_CHECK_LAUNCH();
   return DYB_OK;
 }

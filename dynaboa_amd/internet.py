@@ -4,6 +4,7 @@
     python -m dynaboa_amd.internet --extract DIR        # every DIR/<seq>.json (AlphaPose records) -> DIR/<seq>.npz
     python -m dynaboa_amd.internet --internet_root DIR [--save_res 1] [--native_results 0]
                                    [--split_tracks 1 --min_track_frames N --seqs_per_gpu S --num_shards N]
+                                   [--scene_overlays 1 | --compose_only 1]
 
 The second form is the reference's ``dynaboa_internet.py`` with its flags and defaults: adaptation, then one inference per row, no
 metrics; it writes ``<expdir>/<expname>/result/Pred_{n}.pt`` (``verts``, ``cam``, ``rotmat``, ``beta``) for every row and, with
@@ -23,7 +24,10 @@ What differs from the reference, on purpose:
   * several people of one video can be adapted as separate sequences: ``split_tracks`` makes one sequence per (file, track) instead of
     the reference's single stream over all people interleaved, whose motion term compares a person with whoever stood ``interval``
     rows earlier.  A lockstep step of such sequences cuts all its crops with one ``datasets.preprocess_frames`` call, and a frame
-    that two tracks share is decoded and uploaded once."""
+    that two tracks share is decoded and uploaded once;
+  * ``--scene_overlays 1`` draws, after the adaptation, ONE picture per video frame with every adapted person of that frame in it
+    (``scene/<seq>/<frame>.png``; ``compose_scenes``) - the reference has one picture per person.  ``--compose_only 1`` runs just
+    that pass over the ``result/Pred_{n}.pt`` files of an existing experiment directory (after a sharded run, for one)."""
 from __future__ import annotations
 
 import argparse
@@ -250,6 +254,10 @@ def _make_parser():
     p.add_argument('--split_tracks', type=int, default=0, choices=[0, 1],
                    help="0: one stream over all rows in file order (the reference); 1: one sequence per (file, track)")
     p.add_argument('--min_track_frames', type=int, default=1, help='--split_tracks 1: drop tracks with fewer rows')
+    p.add_argument('--scene_overlays', type=int, default=0, choices=[0, 1],
+                   help='1: after the adaptation draw every frame once with all its adapted people: scene/<seq>/<frame>.png')
+    p.add_argument('--compose_only', type=int, default=0, choices=[0, 1],
+                   help='1: no adaptation - only the --scene_overlays pass over the result/Pred_{n}.pt of <expdir>/<expname>')
     p.set_defaults(dataset='internet', dump_predictions=1, native_results=1)
     return p
 
@@ -367,6 +375,75 @@ def run_tracks(options, dataset: InternetDataset, make_adaptor, num_shards: int 
     return done
 
 
+# ---------------------------------------------------------------------------------------- all people of a frame in one picture
+SCENE_BATCH = 8              # frames drawn per scene call (a 1920 x 1080 frame and its picture are 6 MB each on the device)
+
+
+def scene_path(exppath: str, imgname: str) -> str:
+    """``<exppath>/scene/<seq>/<frame file stem>.png`` for the frame ``<seq>/<file>``."""
+    return os.path.join(exppath, 'scene', os.path.splitext(imgname)[0] + '.png')
+
+
+def scene_meshes(dataset: InternetDataset, exppath: str, rows: Sequence[int], width: int, height: int):
+    """The adapted people of ONE frame (`rows`: its rows) as ``Renderer.render_scenes`` takes them, in painter order: [(verts
+    (6890, 3) fp32, cam (4,) = (sx, sy, tx, ty) fp32 in the frame, colour)] from ``result/Pred_{n}.pt`` - the crop camera recovered
+    from the stored ``cam_t`` (``render.parse_cam``), carried to the frame with the row's box (``convert_crop_cam_to_orig_img``), both
+    in float64 and rounded once.  Every person has a camera of their own, so their depths cannot be compared: the order is by
+    apparent size instead - ascending frame scale sx (the apparently smaller person goes underneath), then track id, then row."""
+    import joblib
+    from .render import convert_crop_cam_to_orig_img, parse_cam, track_color
+    people = []
+    for n in rows:
+        path = os.path.join(exppath, 'result', f'Pred_{n}.pt')
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"scene overlays: row {n} ({dataset.imgnames[n]}, track {int(dataset.tracks[n])}) has no {path}")
+        d = joblib.load(path)
+        cam = parse_cam(np.asarray(d['cam'], np.float64).reshape(1, 3))
+        bbox = np.array([[dataset.centers[n][0], dataset.centers[n][1], float(dataset.scales[n]) * 200]], np.float64)
+        ocam = convert_crop_cam_to_orig_img(cam, bbox, width, height)[0].astype(np.float32)
+        people.append((float(ocam[0]), int(dataset.tracks[n]), int(n), np.asarray(d['verts'], np.float32).reshape(-1, 3), ocam))
+    people.sort(key=lambda p: p[:3])
+    return [(v, ocam, track_color(tr)) for _, tr, _, v, ocam in people]
+
+
+def compose_scenes(dataset: InternetDataset, exppath: str, renderer=None, rows: Optional[Sequence[int]] = None) -> List[str]:
+    """One picture per video frame with every adapted person of it: for each distinct ``imgname`` among `rows` (default: the rows
+    of the dataset's sequences) the frame is decoded once, its people are read from the written ``result/Pred_{n}.pt``
+    (``scene_meshes``: order and colours) and drawn over it by one scene pass (``Renderer.render_scenes``, SCENE_BATCH frames per
+    call) -> ``scene/<seq>/<frame file stem>.png``.  A pass over written results, not part of the frame step: tracks in lockstep
+    reach a video frame at different steps, and ranks own different people.  renderer: a ``render.Renderer`` with the meshes' face
+    table (default: the SMPL model's, as the per-person overlays use).  -> the written paths, in frame order of first appearance."""
+    from PIL import Image
+    if rows is None:
+        rows = [r for s in dataset.sequences for r in s["rows"]]
+    by_frame: Dict[str, List[int]] = {}
+    for n in sorted(int(r) for r in rows):
+        by_frame.setdefault(str(dataset.imgnames[n]), []).append(n)
+    if renderer is None:
+        renderer = scene_renderer(None, dataset.device)
+    names, paths = list(by_frame), []
+    for lo in range(0, len(names), SCENE_BATCH):
+        part = names[lo:lo + SCENE_BATCH]
+        frames = [torch.from_numpy(dataset.read_frame(name)).to(dataset.device) for name in part]
+        scenes = [scene_meshes(dataset, exppath, by_frame[name], int(f.shape[1]), int(f.shape[0])) for name, f in zip(part, frames)]
+        scenes = [[(torch.from_numpy(v).to(dataset.device), torch.from_numpy(c).to(dataset.device), col) for v, c, col in sc] for sc in scenes]
+        for name, pic in zip(part, renderer.render_scenes(frames, scenes)):
+            path = scene_path(exppath, name)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            Image.fromarray(pic.cpu().numpy()).save(path)
+            paths.append(path)
+    return paths
+
+
+def scene_renderer(assets_bundle, device):
+    """The renderer of the scene pass: the face table of the bundle's SMPL model, else of the model files under data/smpl."""
+    from .render import Renderer
+    if assets_bundle is not None:
+        return Renderer(orig_img=True, faces=np.asarray(assets_bundle.smpl_neutral["faces"]), device=device)
+    from .smpl import SMPL
+    return Renderer(orig_img=True, faces=SMPL("data/smpl", create_transl=False).faces, device=device)
+
+
 def run_driver(options, assets_bundle=None, device=None):
     """``python -m dynaboa_amd.internet``: --extract, or the adaptation of <internet_root> - one stream (the reference), or with
     --split_tracks / --seqs_per_gpu / --num_shards the tracks as sequences."""
@@ -380,6 +457,13 @@ def run_driver(options, assets_bundle=None, device=None):
             torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         device = torch.device("cuda", torch.cuda.current_device())
     exppath = os.path.join(options.expdir, options.expname)
+    scene_pass = int(getattr(options, "scene_overlays", 0)) or int(getattr(options, "compose_only", 0))
+    if scene_pass and nsh > 1:
+        raise ValueError("--scene_overlays / --compose_only draw the people of ALL ranks into one picture and there are "
+                         f"{nsh} shards: run the shards without it, then once more with --compose_only 1 and --num_shards 1")
+    if getattr(options, "compose_only", 0):
+        ds = InternetDataset(options, device=device)
+        return compose_scenes(ds, exppath, scene_renderer(assets_bundle, device))
     os.makedirs(exppath, exist_ok=True)
     if rank == 0:
         with open(os.path.join(exppath, 'setting.txt'), 'w') as fh:               # dynaboa_internet.py:176-180
@@ -390,12 +474,17 @@ def run_driver(options, assets_bundle=None, device=None):
     if not (options.split_tracks or S > 1 or nsh > 1):
         ad = Adaptor(options, assets_bundle, device)
         ad.excute()
+        if scene_pass:
+            compose_scenes(ad.dataset, exppath, scene_renderer(assets_bundle, device))
         return list(range(len(ad.dataset)))
     if S > 1:
         from . import native_step as NS
         NS.set_replica_policy(getattr(options, "replica_policy", "throughput") != "bitexact")
     ds = InternetDataset(options, device=device)
-    return run_tracks(options, ds, lambda: Adaptor(copy.copy(options), assets_bundle, device), nsh, rank, S)
+    done = run_tracks(options, ds, lambda: Adaptor(copy.copy(options), assets_bundle, device), nsh, rank, S)
+    if scene_pass:
+        compose_scenes(ds, exppath, scene_renderer(assets_bundle, device), rows=done)
+    return done
 
 
 def main(argv=None):

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import constants as C
 from ._abi import check
 from .hmr import stream_of
 
@@ -53,6 +54,27 @@ class RenderDesc(ctypes.Structure):
     """dyb_render_desc (include/dynaboa_hip.h): one mesh of a ragged call."""
     _fields_ = [("verts", ctypes.c_void_p), ("background", ctypes.c_void_p), ("out", ctypes.c_void_p), ("H", ctypes.c_int),
                 ("W", ctypes.c_int)]
+
+
+class RenderScene(ctypes.Structure):
+    """dyb_render_scene (include/dynaboa_hip.h): one scene of a scene call."""
+    _fields_ = [("background", ctypes.c_void_p), ("out", ctypes.c_void_p), ("mesh_id", ctypes.c_void_p), ("face_id", ctypes.c_void_p),
+                ("H", ctypes.c_int), ("W", ctypes.c_int), ("mesh_begin", ctypes.c_int), ("mesh_end", ctypes.c_int)]
+
+
+def parse_cam(cam_t):
+    """The crop camera (s, tx, ty) back from the ``cam_t`` = (tx, ty, 2 f / (224 s + 1e-9)) that the ``Pred_{n}.pt`` dumps store
+    (reference render_demo.py:162-166).  cam_t (B, 3), numpy or torch -> (B, 3) of the same kind."""
+    stack = torch.stack if torch.is_tensor(cam_t) else np.stack
+    s = (2 * C.FOCAL_LENGTH / cam_t[:, 2] - 1e-9) / C.IMG_RES
+    return stack([s, cam_t[:, 0], cam_t[:, 1]], 1)
+
+
+def track_color(track: int) -> Tuple[float, float, float]:
+    """The colour a tracked person is drawn in: constants.TRACK_COLORS by track id modulo its length; a detection without a track
+    (-1) takes entry 0, the reference's colour."""
+    r, g, b = C.TRACK_COLORS[int(track) % len(C.TRACK_COLORS) if track >= 0 else 0]
+    return (r / 255.0, g / 255.0, b / 255.0)
 
 
 class Renderer:
@@ -198,6 +220,104 @@ class Renderer:
                                         col[0], col[1], col[2], N, V, F, 0 if box else 1, ws.data_ptr(), ws.numel(), stream_of(c)),
               "dyb_render_meshes_var")
         return outs
+
+    def render_scenes(self, frames, scenes, return_ids: bool = False):
+        """Scenes: several meshes over ONE frame each (all tracked people of a video frame), drawn by dyb_render_scenes.  frames[k]:
+        uint8 RGB (H, W, 3) on the device or None (black at `resolution`); scenes[k]: a list of (verts (V, 3), cam (4,) = (sx, sy, tx,
+        ty), color (3,)) in painter order - there is no depth test between meshes (each has its own camera, their Z are not
+        comparable): the LAST listed mesh is on top wherever it covers a pixel.  A scene may be empty.
+        -> list of uint8 (H, W, 3) tensors, scene k equal byte for byte to the chain  img = frames[k]; for v, c, col in scenes[k]:
+        img = render(img, v, c, color=col)  on a renderer of that size.  return_ids: -> (pictures, mesh_ids, face_ids), int32 (H, W)
+        each: the winning mesh's position in scenes[k] and its face, -1 where nothing is drawn.
+        One call draws at most 64 scenes and 64 meshes; more are packed into several calls, a scene never split - a scene of more
+        than 64 meshes is a ValueError."""
+        K = len(scenes)
+        if len(frames) != K:
+            raise ValueError("render_scenes takes one frame (or None) per scene")
+        for sc in scenes:
+            if len(sc) > MAX_MESHES:
+                raise ValueError(f"a scene holds at most {MAX_MESHES} meshes, not {len(sc)}")
+        pics, mids, fids = [], [], []
+        lo = 0
+        while lo < K:
+            hi, nm = lo, 0
+            while hi < K and hi - lo < MAX_MESHES and nm + len(scenes[hi]) <= MAX_MESHES:
+                nm += len(scenes[hi])
+                hi += 1
+            p, m, f = self._scene_call(frames[lo:hi], scenes[lo:hi], return_ids)
+            pics += p
+            mids += m
+            fids += f
+            lo = hi
+        return (pics, mids, fids) if return_ids else pics
+
+    def _scene_call(self, frames, scenes, ids):
+        meshes = [m for sc in scenes for m in sc]
+        dev = self._device_of(*frames, *(m[0] for m in meshes))
+        M = len(meshes)
+        V = int(meshes[0][0].shape[0]) if M else self.min_verts
+        if V < self.min_verts:
+            raise ValueError(f"faces index vertex {self.min_verts - 1} but the mesh has {V} vertices")
+        lib = _lib.load()
+        faces, ptr, idx = self._adjacency(V, dev)
+        F = int(faces.shape[0])
+        desc = (RenderScene * len(scenes))()
+        vptr, mscene = (ctypes.c_void_p * max(M, 1))(), (ctypes.c_int * max(M, 1))()
+        keep, pics, mids, fids, cams, cols = [], [], [], [], [], []
+        at = 0
+        for k, (bg, sc) in enumerate(zip(frames, scenes)):
+            if bg is None:
+                W, H = self.resolution
+            else:
+                bg = torch.as_tensor(bg).to(dev)
+                if bg.dtype != torch.uint8 or bg.dim() != 3 or bg.shape[2] != 3:
+                    raise ValueError("the frame under the meshes must be uint8 RGB (H, W, 3)")
+                bg = bg.contiguous()
+                H, W = int(bg.shape[0]), int(bg.shape[1])
+            if not (0 < H <= MAX_DIM and 0 < W <= MAX_DIM):
+                raise ValueError(f"frame size {(H, W)} outside 1 .. {MAX_DIM}")
+            out = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+            mid = torch.empty(H, W, dtype=torch.int32, device=dev) if ids else None
+            fid = torch.empty(H, W, dtype=torch.int32, device=dev) if ids else None
+            for v, cam, col in sc:
+                v = torch.as_tensor(v).detach()
+                if v.dtype != torch.float32 or not v.is_contiguous() or v.device != dev:
+                    v = v.to(dev, torch.float32).contiguous()
+                if tuple(v.shape) != (V, 3):
+                    raise ValueError("the meshes of a call must be (V, 3) each, with one V")
+                vptr[at], mscene[at] = v.data_ptr(), k
+                keep.append(v)
+                cams.append(torch.as_tensor(cam).detach().to(dev, torch.float32).reshape(4))
+                cols.append([float(x) for x in col])
+                at += 1
+            desc[k] = RenderScene(bg.data_ptr() if bg is not None else None, out.data_ptr(), mid.data_ptr() if ids else None,
+                                  fid.data_ptr() if ids else None, H, W, at - len(sc), at)
+            keep.append(bg)
+            pics.append(out)
+            if ids:
+                mids.append(mid)
+                fids.append(fid)
+        cam = torch.stack(cams).contiguous() if M else None
+        colors = torch.tensor(cols, dtype=torch.float32).reshape(M, 3).to(dev) if M else None
+        nbytes = int(lib.dyb_render_scenes_workspace_bytes(M, V, F))
+        sid = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+        ws = self._ws.get((str(dev), sid))
+        if ws is None or ws.numel() < nbytes:
+            ws = self._ws[(str(dev), sid)] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        check(lib.dyb_render_scenes(ctypes.cast(desc, ctypes.c_void_p), len(scenes), ctypes.cast(vptr, ctypes.c_void_p),
+                                    ctypes.cast(mscene, ctypes.c_void_p), cam.data_ptr() if M else None, colors.data_ptr() if M else None,
+                                    faces.data_ptr(), ptr.data_ptr(), idx.data_ptr(), M, V, F, 0, ws.data_ptr(), ws.numel(), stream_of(ws)),
+              "dyb_render_scenes")
+        return pics, mids, fids
+
+    def render_scene(self, frame, verts_list, cams, colors=None):
+        """One scene: the meshes verts_list[i] (V, 3) under cams[i] = (sx, sy, tx, ty), in painter order (the last on top), over
+        `frame` (uint8 (H, W, 3) or None).  colors: one (r, g, b) per mesh; None gives every mesh DEFAULT_COLOR.  -> uint8 (H, W, 3)."""
+        n = len(verts_list)
+        if len(cams) != n or (colors is not None and len(colors) != n):
+            raise ValueError("render_scene takes one camera (and one colour) per mesh")
+        cols = [DEFAULT_COLOR] * n if colors is None else colors
+        return self.render_scenes([frame], [[(verts_list[i], cams[i], cols[i]) for i in range(n)]])[0]
 
     def render(self, img, verts, cam, angle=None, axis=None, mesh_filename=None, color: Sequence[float] = DEFAULT_COLOR):
         """The mesh (or batch of meshes) drawn over ``img`` (uint8 RGB, (H, W, 3) or (N, H, W, 3); None = black), as uint8 of the

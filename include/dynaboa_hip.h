@@ -532,6 +532,37 @@ size_t dyb_render_var_workspace_bytes(int N, int V, int F);
 int dyb_render_meshes_var(const dyb_render_desc* desc, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
                           float col_r, float col_g, float col_b, int N, int V, int F, int flags, void* ws, size_t ws_bytes,
                           dyb_stream_t stream);
+/* Scenes: several meshes over ONE frame (all tracked people of a video frame in one overlay), up to 64 scenes and 64 meshes in
+ * one call.  Every mesh has its own weak-perspective camera, so depths of different meshes are not comparable and there is NO
+ * depth test between meshes - the painter rule instead: within a mesh the nearest face wins (ties: lower face index), between
+ * meshes the one listed LATER wins wherever it covers a pixel, whatever its Z.  A scene equals, byte for byte, the chain
+ * img = frame; for i in its range: img = dyb_render_meshes(mesh i over img, colour i) - drawn in one pass: one workgroup per tile
+ * walks the scene's meshes from the last to the first, skips a mesh whose pixel box misses the tile, stops testing a pixel once a
+ * mesh has claimed it, leaves when every pixel of the tile is decided and shades each pixel once; the frame is read and written once.
+ * scenes: HOST table of nscenes entries - background [H][W][3] uint8 (device) or NULL (black), out [H][W][3] uint8 (device),
+ * mesh_id / face_id [H][W] int32 (device, optional: NULL): the winning mesh's position in the scene's own list and its face, -1
+ * where nothing is drawn; [mesh_begin, mesh_end): the scene's meshes in the call's mesh list - the ranges tile 0 .. nmeshes in scene
+ * order, a scene may be empty (its picture is its frame, or black).  mesh_verts: HOST table of nmeshes device pointers to [V][3]
+ * fp32 rows (views into different buffers are fine); mesh_scene: HOST table, the scene of each mesh (must agree with the ranges);
+ * cam [nmeshes][4] = (sx, sy, tx, ty) and colors [nmeshes][3] fp32 are DEVICE arrays.  A mesh is set up on its scene's H, W.  The
+ * tables travel as kernel arguments: no allocation, no copy, no host wait; they may be reused when the call returns.  flags bit 0
+ * set: no per-mesh pixel box (same bytes, for measurements); other bits 0.  With nmeshes == 0 mesh_verts, mesh_scene, cam, colors
+ * and ws may be NULL.  DYB_ERR_ARG: a NULL required argument, nscenes <= 0, nmeshes < 0, non-positive size, ranges that do not
+ * tile the list or disagree with mesh_scene; DYB_ERR_UNSUPPORTED: nscenes or nmeshes > 64, H or W > 4096; DYB_ERR_WORKSPACE:
+ * ws_bytes < dyb_render_scenes_workspace_bytes(nmeshes, V, F).  Everything is checked before the first launch: nothing is written
+ * when an error code is returned. */
+typedef struct dyb_render_scene {
+  const uint8_t* background;
+  uint8_t* out;
+  int* mesh_id;
+  int* face_id;
+  int H, W;
+  int mesh_begin, mesh_end;
+} dyb_render_scene;
+size_t dyb_render_scenes_workspace_bytes(int nmeshes, int V, int F);
+int dyb_render_scenes(const dyb_render_scene* scenes, int nscenes, const float* const* mesh_verts, const int* mesh_scene,
+                      const float* cam, const float* colors, const int* faces, const int* adj_ptr, const int* adj_idx, int nmeshes,
+                      int V, int F, int flags, void* ws, size_t ws_bytes, dyb_stream_t stream);
 
 /* ---- native frame stepper: Adaptor.adaptation (reference dynaboa_benchmark.py:126-193) as ONE call per frame --------
  * The first-order bilevel schedule with the frame-loss set - clone, inner_step x [lower-level loss

@@ -1,0 +1,318 @@
+"""The scene entry (dyb_render_scenes, Renderer.render_scenes / render_scene): several meshes over ONE frame in one pass - on the
+kernel emulator here, on cuda:0 under `-m gpu`.
+
+The rule is the painter's: no depth between meshes (each has its own weak-perspective camera), the mesh listed later is on top.  The
+oracle for the pictures is the chain  img = frame; for mesh in order: img = Renderer.render(img, mesh)  on the same device (which
+tests/test_render.py pins against tests/render_ref.py): equal bytes.  The mesh_id / face_id maps are compared with the same chain
+built from tests/render_ref.render (tests/scene_ref.py): equal integers.  Nothing here has a tolerance."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import scene_ref as SR
+from test_render import icosphere, smpl_case
+
+_EMU = {}
+_REF = {}
+COLORS = [(205 / 255.0, 129 / 255.0, 98 / 255.0), (0.2, 0.9, 0.4), (0.35, 0.45, 1.0)]
+
+
+@pytest.fixture
+def emu_lib():
+    from emu.build_emu import build
+    from dynaboa_amd import _abi, _lib
+    if "lib" not in _EMU:
+        _EMU["lib"] = _abi.bind(ctypes.CDLL(build()))
+    saved = _lib._lib
+    _lib.use_library(_EMU["lib"])
+    yield _EMU["lib"]
+    _lib._lib = saved
+
+
+@pytest.fixture(params=["emu", pytest.param("gpu", marks=pytest.mark.gpu)])
+def dev(request):
+    if request.param == "emu":
+        request.getfixturevalue("emu_lib")
+        return "cpu"
+    return "cuda:0"
+
+
+# ---------------------------------------------------------------------------- helpers
+def T(a, dev, dt=np.float32):
+    return torch.as_tensor(np.asarray(a, dt)).to(dev)
+
+
+def sphere(level, radius=1.0, z=3.0):
+    v, f = icosphere(level)
+    v = (v * radius).astype(np.float32)
+    v[:, 2] += z
+    return v, f
+
+
+def frame(H, W, seed=0):
+    return np.random.default_rng(seed).integers(0, 256, (H, W, 3), dtype=np.uint8)
+
+
+def chain(dev, faces, meshes, H, W, bg):
+    """img = frame; for mesh in order: img = Renderer.render(img, mesh) - the oracle for the pictures."""
+    from dynaboa_amd.render import Renderer
+    r = Renderer(resolution=(W, H), faces=faces, device=dev)
+    img = None if bg is None else T(bg, dev, np.uint8)
+    if not meshes:
+        return np.zeros((H, W, 3), np.uint8) if bg is None else np.array(bg)
+    for v, cam, col in meshes:
+        img = r.render(img, T(v, dev), T(cam, dev), color=col)
+    return img.cpu().numpy()
+
+
+def draw(dev, faces, frames, scenes, resolution=(16, 16), rows=None):
+    """One render_scenes call with ids.  rows: device views to use as the vertex rows (else the arrays are uploaded)."""
+    from dynaboa_amd.render import Renderer
+    r = Renderer(resolution=resolution, faces=faces, device=dev)
+    k = 0
+    sc = []
+    for s in scenes:
+        sc.append([])
+        for v, cam, col in s:
+            sc[-1].append((rows[k] if rows is not None else T(v, dev), T(cam, dev), col))
+            k += 1
+    pics, mids, fids = r.render_scenes([None if b is None else T(b, dev, np.uint8) for b in frames], sc, return_ids=True)
+    return [p.cpu().numpy() for p in pics], [m.cpu().numpy() for m in mids], [f.cpu().numpy() for f in fids]
+
+
+def ref_ids(key, meshes, faces, H, W):
+    """One scene_ref chain per case, shared by the emulator and the GPU run of a session; never modified."""
+    if key not in _REF:
+        _REF[key] = SR.render_scene(meshes, faces, H, W)[1:]
+    return _REF[key]
+
+
+def check_scene(dev, key, faces, meshes, H, W, bg, got):
+    pic, mid, fid = got
+    want = chain(dev, faces, meshes, H, W, bg)
+    assert pic.dtype == np.uint8 and pic.shape == (H, W, 3) and pic.tobytes() == want.tobytes(), key
+    rmid, rfid = ref_ids(key, meshes, faces, H, W)
+    assert mid.dtype == np.int32 and np.array_equal(mid, rmid), (key, int((mid != rmid).sum()))
+    assert fid.dtype == np.int32 and np.array_equal(fid, rfid), (key, int((fid != rfid).sum()))
+    return want, rmid
+
+
+# ---------------------------------------------------------------------------- the painter rule
+@pytest.mark.parametrize("H,W", [(24, 40), (32, 48)], ids=["narrow40x24", "wide48x32"])
+def test_two_overlapping_spheres_both_orders(dev, H, W):
+    """A (nearer: smaller Z) left of centre, B right of centre, overlapping in the middle.  Listed (A, B), B is on top in the overlap
+    although A is nearer - a shared depth buffer would show A there."""
+    va, faces = sphere(2, z=2.0)
+    vb, _ = sphere(2, z=6.0)
+    A = (va, [0.55, 0.8, -0.45, 0.05], COLORS[0])
+    B = (vb, [0.55, 0.8, 0.45, -0.05], COLORS[1])
+    bg = frame(H, W, seed=H)
+    pics, mids, fids = draw(dev, faces, [bg, bg], [[A, B], [B, A]])
+    ab, mid_ab = check_scene(dev, ("two", H, W, "ab"), faces, [A, B], H, W, bg, (pics[0], mids[0], fids[0]))
+    ba, mid_ba = check_scene(dev, ("two", H, W, "ba"), faces, [B, A], H, W, bg, (pics[1], mids[1], fids[1]))
+    assert ab.tobytes() != ba.tobytes()
+    import render_ref as RR
+    both = (RR.render(va, faces, A[1], H, W).face_id >= 0) & (RR.render(vb, faces, B[1], H, W).face_id >= 0)
+    assert both.sum() > 30 and float(va[:, 2].max()) < float(vb[:, 2].min())           # A is nearer everywhere
+    assert np.all(mids[0][both] == 1) and np.all(mids[1][both] == 1)                     # ... and the later mesh wins all the same
+    assert (mids[0] == 0).sum() > 30 and (mids[0] == -1).sum() > 30
+
+
+def test_three_spheres_three_colours(dev):
+    v, faces = sphere(1)
+    meshes = [(v, [0.5, 0.7, -0.6, -0.2], COLORS[0]), (v * np.float32(0.8), [0.6, 0.6, 0.1, 0.3], COLORS[1]),
+              (v * np.float32(1.1), [0.45, 0.5, 0.5, -0.3], COLORS[2])]
+    bg = frame(37, 53, seed=1)
+    pics, mids, fids = draw(dev, faces, [bg], [meshes])
+    _, mid = check_scene(dev, "three colours", faces, meshes, 37, 53, bg, (pics[0], mids[0], fids[0]))
+    assert all((mid == k).sum() > 20 for k in range(3))
+    # every mesh in the first colour draws something else
+    assert draw(dev, faces, [bg], [[(m[0], m[1], COLORS[0]) for m in meshes]])[0][0].tobytes() != pics[0].tobytes()
+    # render_scene: the one-scene form; colors = None is DEFAULT_COLOR for every mesh
+    from dynaboa_amd.render import DEFAULT_COLOR, Renderer
+    r = Renderer(resolution=(53, 37), faces=faces, device=dev)
+    one = r.render_scene(T(bg, dev, np.uint8), [T(m[0], dev) for m in meshes], [T(m[1], dev) for m in meshes], [m[2] for m in meshes])
+    assert one.cpu().numpy().tobytes() == pics[0].tobytes()
+    plain = r.render_scene(T(bg, dev, np.uint8), [T(m[0], dev) for m in meshes], [T(m[1], dev) for m in meshes])
+    assert plain.cpu().numpy().tobytes() == chain(dev, faces, [(m[0], m[1], DEFAULT_COLOR) for m in meshes], 37, 53, bg).tobytes()
+
+
+def test_three_scenes_one_call(dev):
+    """Sizes (33, 20), (16, 16), (48, 64) (H, W), mesh counts 1, 3 and 0, the vertex rows views at unequal strides inside one
+    NaN-filled buffer, the second frame None (black)."""
+    from dynaboa_amd.render import Renderer
+    v, faces = sphere(1)
+    V = len(v)
+    meshes = [(v, [0.7, 0.6, 0.1, -0.1], COLORS[0]),
+              (v * np.float32(0.7), [0.8, 0.8, -0.4, 0.0], COLORS[1]), (v * np.float32(0.9), [0.6, 0.7, 0.3, 0.2], COLORS[2]),
+              (v * np.float32(0.5), [0.9, 0.9, 0.0, -0.3], COLORS[0])]
+    gaps = [5 + 7 * i for i in range(4)]
+    buf = torch.full((sum(gaps) + 4 * V * 3 + 3,), float("nan"), dtype=torch.float32, device=dev)
+    rows, at = [], 0
+    for m, g in zip(meshes, gaps):
+        at += g
+        buf[at:at + V * 3] = T(m[0], dev).reshape(-1)
+        rows.append(buf[at:at + V * 3].view(V, 3))
+        at += V * 3
+    bgs = [frame(33, 20, seed=2), None, frame(48, 64, seed=3)]
+    scenes = [meshes[:1], meshes[1:], []]
+    pics, mids, fids = draw(dev, faces, bgs, scenes, resolution=(16, 16), rows=rows)
+    for k, (H, W) in enumerate([(33, 20), (16, 16), (48, 64)]):
+        check_scene(dev, ("three scenes", k), faces, scenes[k], H, W, bgs[k], (pics[k], mids[k], fids[k]))
+    assert (pics[0] != bgs[0]).any() and (mids[1] == 2).sum() > 10 and (mids[1] == 1).sum() > 10
+    assert pics[2].tobytes() == bgs[2].tobytes() and np.all(mids[2] == -1) and np.all(fids[2] == -1)      # the empty scene: its frame
+    r = Renderer(resolution=(16, 16), faces=faces, device=dev)
+    many = r.render_many([T(bgs[0], dev, np.uint8)], rows[:1], T([meshes[0][1]], dev), color=COLORS[0])
+    assert many[0].cpu().numpy().tobytes() == pics[0].tobytes()
+    # an empty scene over no frame: black
+    assert not r.render_scenes([None], [[]])[0].cpu().numpy().any()
+
+
+def test_mesh_off_the_image_and_nan_rows_leave_no_trace(dev):
+    v, faces = sphere(1)
+    nan = np.full_like(v, np.nan)
+    half = v.copy()
+    half[::2] = np.nan                                     # every face of it has a NaN corner or draws as in the chain
+    meshes = [(v, [0.6, 0.6, 0.0, 0.0], COLORS[0]), (v, [0.5, 0.5, 7.0, 0.0], COLORS[1]), (nan, [0.6, 0.6, 0.0, 0.0], COLORS[2]),
+              (half, [0.7, 0.7, 0.2, 0.1], COLORS[1])]
+    bg = frame(40, 56, seed=4)
+    pics, mids, fids = draw(dev, faces, [bg], [meshes])
+    _, mid = check_scene(dev, "off and nan", faces, meshes, 40, 56, bg, (pics[0], mids[0], fids[0]))
+    assert not (mid == 1).any() and not (mid == 2).any() and (mid == 0).sum() > 50
+    alone = draw(dev, faces, [bg], [[meshes[0], meshes[3]]])
+    assert alone[0][0].tobytes() == pics[0].tobytes()
+
+
+@pytest.mark.parametrize("front", ["whole", "left"])
+def test_front_mesh_decides_its_tiles(dev, front):
+    """32 x 32 (four tiles).  The last listed sphere covers the whole picture (every tile leaves the walk after one mesh), or all of
+    the two left tiles and a part of the right ones (the left tiles leave, the right ones go on to the mesh beneath)."""
+    v, faces = sphere(2)
+    under = (v, [0.7, 0.7, 0.1, -0.1], COLORS[1])
+    # whole: radius 2.2 half pictures about the centre; left: radius 24 px about (0, 16) - the far corners of the left tiles lie at 21.9
+    top = (v, [2.2, 2.2, 0.0, 0.0], COLORS[0]) if front == "whole" else (v, [1.5, 1.5, -1.0 / 1.5, 0.0], COLORS[0])
+    bg = frame(32, 32, seed=5)
+    pics, mids, fids = draw(dev, faces, [bg], [[under, top]])
+    _, mid = check_scene(dev, ("front", front), faces, [under, top], 32, 32, bg, (pics[0], mids[0], fids[0]))
+    if front == "whole":
+        assert np.all(mid == 1)
+    else:
+        assert np.all(mid[:, :16] == 1) and (mid[:, 16:] == 0).sum() > 30 and (mid[:, 16:] == 1).sum() > 30 and np.all(mid[:, 26:] != 1)
+
+
+def test_more_than_256_faces_over_a_tile(dev, smpl_tabs):
+    """Two synthetic SMPL meshes (random vertex triples: hundreds of faces over every tile) at 32 x 32: the upper mesh decides
+    some pixels of a tile and the chunks of the lower one are streamed with those pixels sitting out."""
+    verts, faces, cams = smpl_case(dev, smpl_tabs, 2000)
+    meshes = [(verts[0], cams[0], COLORS[0]), (verts[1], cams[1] * np.array([0.8, 0.8, 1.0, 1.0], np.float32), COLORS[1])]
+    bg = frame(32, 32, seed=6)
+    pics, mids, fids = draw(dev, faces, [bg], [meshes])
+    _, mid = check_scene(dev, ("smpl", dev), faces, meshes, 32, 32, bg, (pics[0], mids[0], fids[0]))
+    tiles = [mid[ty:ty + 16, tx:tx + 16] for ty in (0, 16) for tx in (0, 16)]
+    assert sum(int((t == 1).sum() > 20 and (t == 0).sum() > 20) for t in tiles) >= 2      # tiles decided in part after the upper mesh
+
+
+# ---------------------------------------------------------------------------- limits, error codes
+def small_case(n, seed):
+    v0, f0 = icosphere(0)
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(n):
+        v = (v0 * (0.5 + 0.5 * rng.random())).astype(np.float32)
+        v[:, 2] += 3.0
+        cam = [0.5 + 0.4 * rng.random(), 0.5 + 0.4 * rng.random(), 1.2 * rng.random() - 0.6, 1.2 * rng.random() - 0.6]
+        out.append((v, cam, COLORS[k % 3]))
+    return out, f0
+
+
+def test_sixty_four_scenes_one_call_and_two_calls_agree(dev):
+    from dynaboa_amd import _lib
+    meshes, f0 = small_case(64, 7)
+    bgs = [frame(16, 16, seed=100 + k) for k in range(64)]
+    calls = []
+    lib = _lib.load()
+    real = lib.dyb_render_scenes
+    try:
+        lib.dyb_render_scenes = lambda *a: (calls.append(a[1]), real(*a))[1]
+        got = draw(dev, f0, bgs, [[m] for m in meshes])
+        again = draw(dev, f0, bgs, [[m] for m in meshes])
+        assert calls == [64, 64]
+        # 65 one-mesh scenes: two calls, no scene split
+        more = draw(dev, f0, bgs + [bgs[0]], [[m] for m in meshes] + [[meshes[0]]])
+        assert calls[2:] == [64, 1]
+    finally:
+        lib.dyb_render_scenes = real
+    for a, b in zip(got, again):
+        assert [x.tobytes() for x in a] == [x.tobytes() for x in b]
+    for k in range(64):
+        assert got[0][k].tobytes() == chain(dev, f0, [meshes[k]], 16, 16, bgs[k]).tobytes() == more[0][k].tobytes(), k
+    assert more[0][64].tobytes() == got[0][0].tobytes()
+
+
+def test_sixty_four_meshes_one_scene(dev):
+    from dynaboa_amd.render import Renderer
+    meshes, f0 = small_case(64, 8)
+    bg = frame(16, 16, seed=9)
+    pics, mids, fids = draw(dev, f0, [bg], [meshes])
+    _, mid = check_scene(dev, "64 meshes", f0, meshes, 16, 16, bg, (pics[0], mids[0], fids[0]))
+    assert len(np.unique(mid)) > 5
+    r = Renderer(resolution=(16, 16), faces=f0, device=dev)
+    with pytest.raises(ValueError, match="64"):
+        r.render_scenes([T(bg, dev, np.uint8)], [[(T(m[0], dev), T(m[1], dev), m[2]) for m in meshes + meshes[:1]]])
+    # scenes of 40 + 40 meshes: two calls (a scene is never split)
+    two = r.render_scenes([T(bg, dev, np.uint8)] * 2, [[(T(m[0], dev), T(m[1], dev), m[2]) for m in part] for part in (meshes[:40], meshes[24:])])
+    assert two[1].cpu().numpy().tobytes() == chain(dev, f0, meshes[24:], 16, 16, bg).tobytes()
+
+
+def test_error_codes_write_nothing(dev):
+    from dynaboa_amd import _lib
+    from dynaboa_amd.render import RenderScene, vertex_face_csr
+    lib = _lib.load()
+    v, f = icosphere(0)
+    v = v.copy()
+    v[:, 2] += 3.0
+    ptr, idx = vertex_face_csr(f, len(v))
+    verts, faces, ptr, idx = T(v, dev), T(f, dev, np.int32), T(ptr, dev, np.int32), T(idx, dev, np.int32)
+    cam = T(np.tile(np.array([[0.8, 0.8, 0, 0]], np.float32), (65, 1)), dev)
+    col = T(np.ones((65, 3), np.float32), dev)
+    out = torch.full((2, 16, 16, 3), 91, dtype=torch.uint8, device=dev)
+    ids = torch.full((2, 2, 16, 16), 91, dtype=torch.int32, device=dev)
+    nbytes = int(lib.dyb_render_scenes_workspace_bytes(65, len(v), len(f)))
+    assert nbytes == int(lib.dyb_render_var_workspace_bytes(65, len(v), len(f))) > 0
+    assert lib.dyb_render_scenes_workspace_bytes(0, len(v), len(f)) == 0
+    ws = torch.full((nbytes,), 91, dtype=torch.uint8, device=dev)
+    st = torch.cuda.current_stream().cuda_stream if dev != "cpu" else None
+
+    def call(counts, wsb=nbytes, H=16, W=16, null=None, scene_of=None, begin0=0):
+        M = sum(counts)
+        desc = (RenderScene * len(counts))()
+        at = begin0
+        for k, n in enumerate(counts):
+            desc[k] = RenderScene(None, out[k % 2].data_ptr(), ids[k % 2, 0].data_ptr(), ids[k % 2, 1].data_ptr(), H, W, at, at + n)
+            at += n
+        vp = (ctypes.c_void_p * max(M, 1))(*[verts.data_ptr()] * M)
+        ms = (ctypes.c_int * max(M, 1))(*(scene_of if scene_of is not None else [k for k, n in enumerate(counts) for _ in range(n)]))
+        if null == "out":
+            desc[0].out = None
+        if null == "verts":
+            vp[0] = None
+        return lib.dyb_render_scenes(ctypes.cast(desc, ctypes.c_void_p) if null != "scenes" else None, len(counts),
+                                     ctypes.cast(vp, ctypes.c_void_p), ctypes.cast(ms, ctypes.c_void_p),
+                                     cam.data_ptr() if null != "cam" else None, col.data_ptr() if null != "colors" else None,
+                                     faces.data_ptr(), ptr.data_ptr(), idx.data_ptr(), M, len(v), len(f), 0, ws.data_ptr(), wsb, st)
+    assert call([65]) == -3 and call([33, 32]) == -3 and call([0] * 65) == -3            # DYB_ERR_UNSUPPORTED: 65 meshes / scenes
+    assert call([1], H=4097) == -3 and call([1], W=4097) == -3
+    for null in ("scenes", "out", "verts", "cam", "colors"):                             # DYB_ERR_ARG
+        assert call([1, 1], null=null) == -1, null
+    assert call([]) == -1 and call([1], H=0) == -1 and call([1], W=-4) == -1
+    assert call([1, 1], scene_of=[0, 0]) == -1 and call([1, 1], begin0=1) == -1          # ranges and mesh_scene must agree
+    assert call([1, 1], wsb=int(lib.dyb_render_scenes_workspace_bytes(2, len(v), len(f))) - 1) == -4      # DYB_ERR_WORKSPACE
+    if dev != "cpu":
+        torch.cuda.synchronize()
+    assert bool((out == 91).all()) and bool((ids == 91).all()) and bool((ws == 91).all())
+    assert call([1, 0]) == 0
+    if dev != "cpu":
+        torch.cuda.synchronize()
+    assert bool((out[0] != 91).any()) and bool((out[1] == 0).all()) and bool((ids[1] == -1).all()) and bool((ids[0, 0] == 0).any())
