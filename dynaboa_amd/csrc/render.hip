@@ -24,13 +24,15 @@
 //                    pixel = round(255 I colour).  This is NOT pyrender's metallic-roughness shading (unpinned: pyrender is
 //                    absent from the build image); geometry, visibility and the light set-up are the reference's.
 //
-// Three kernels: vertex normals (one thread per vertex), face set-up (one thread per face: snapped corners + pixel box, an empty
-// box for culled / off-image faces), and one workgroup per 16x16 pixel tile that streams the face boxes 256 at a time, compacts
-// the faces touching the tile into LDS (with their corners and depths) and lets each thread keep the nearest face of its pixel.
-// The list is processed chunk by chunk, so no per-tile capacity can overflow (the synthetic SMPL's random-triple faces put
-// thousands of faces over one tile).
+// Four kernels behind the three entries (uniform: N meshes at one frame size; ragged: every mesh over a frame of its own size;
+// scenes: several meshes over one frame): vertex normals (one thread per vertex), face set-up (one thread per face: snapped corners
+// + pixel box, an empty box for culled / off-image faces), the pixel box of a whole mesh (one workgroup per mesh; ragged and scene
+// entries), and one workgroup per 16x16 pixel tile that streams the face boxes 256 at a time, compacts the faces touching the tile
+// into LDS (with their corners and depths) and lets each thread keep the nearest face of its pixel.  The list is processed chunk by
+// chunk, so no per-tile capacity can overflow (the synthetic SMPL's random-triple faces put thousands of faces over one tile).
 //
-// The scene entry (end of the file) draws several meshes over ONE frame with the same bodies.  Between meshes there is no depth
+// The three entries are one problem at three levels of generality and run the same kernels on one table (RndTab): a ragged mesh is
+// a scene of one mesh, a uniform batch a ragged call whose pointers are strided.  Between the meshes of a scene there is no depth
 // test - each has a camera of its own, their Z are not comparable - but the painter rule: the mesh listed later is on top.
 #include "dyb_common.h"
 
@@ -56,19 +58,6 @@ struct dyb_render_desc {
   uint8_t* out;
   int H, W;
 };
-// mesh descriptors of a ragged call as the kernels see them (kernel arguments: no allocation, no copy, no host wait): every mesh has
-// its own vertex rows, frame and size; tile0 is the prefix of the meshes' tile counts (the flat tile grid of the ragged tile kernel)
-struct RndMesh {
-  const float* verts;
-  const uint8_t* bg;
-  uint8_t* out;
-  int H, W;
-};
-struct RndVarTab {
-  RndMesh m[RND_MAX_N];
-  int tile0[RND_MAX_N + 1];
-};
-
 // one scene of a scene call (include/dynaboa_hip.h declares the same struct): meshes [mesh_begin, mesh_end) of the call's mesh list
 // over one frame, in painter order
 struct dyb_render_scene {
@@ -79,8 +68,10 @@ struct dyb_render_scene {
   int H, W;
   int mesh_begin, mesh_end;
 };
-// a scene call as the kernels see it, again as kernel arguments - sizes and mesh ranges packed so that 64 scenes and 64 meshes stay
-// well inside the 4 KB a launch may carry (cameras and colours are device arrays for the same reason)
+// A call of any of the three entries as the kernels see it: scenes (a frame and the meshes [m0, m1) of the call's list over it, in
+// painter order) and meshes, as kernel arguments - no allocation, no copy, no host wait.  Sizes and mesh ranges are packed so that
+// 64 scenes and 64 meshes fit in the 4 KB a launch may carry (cameras and the scene entry's colours are device arrays for the same
+// reason).  tile0 is the prefix of the scenes' tile counts: the flat grid of the tile kernel.
 struct RndScene {
   const uint8_t* bg;
   uint8_t* out;
@@ -89,13 +80,16 @@ struct RndScene {
   unsigned short H, W;                    // <= RND_MAX_DIM
   unsigned char m0, m1;                   // meshes [m0, m1) of the list, <= RND_MAX_N
 };
-struct RndSceneTab {
+struct RndTab {
   RndScene s[RND_MAX_N];
   const float* verts[RND_MAX_N];          // per mesh
   int tile0[RND_MAX_N + 1];               // prefix of the scenes' tile counts
   unsigned char scene_of[RND_MAX_N];      // per mesh
 };
-static_assert(sizeof(RndSceneTab) <= 3584, "the scene table and the other arguments of a launch must fit in 4 KB");
+// The fattest launch is the tile kernel's: the table (64 * 40 + 64 * 8 + 65 * 4 + 64 = 3396, padded to 3400), then nscenes and its
+// padding (8), seven pointers (56), cr / cg / cb and V / F / use_box (24) = 3488 bytes of explicit arguments, and the 256 bytes of
+// implicit arguments the runtime appends.
+static_assert(sizeof(RndTab) + 8 + 56 + 24 + 256 <= 4096, "the table and the other arguments of the tile launch must fit in 4 KB");
 
 // ---- vertex normals ------------------------------------------------------------------------------------------------------------
 // vertex v of the mesh at P -> its normal at o
@@ -123,24 +117,8 @@ __device__ __forceinline__ void render_vnormal_body(const float* __restrict__ P,
   o[1] = sy * inv;
   o[2] = sz * inv;
 }
-__global__ __launch_bounds__(256) void render_vnormal_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                             const int* __restrict__ adj_ptr, const int* __restrict__ adj_idx, int V,
-                                                             int F, float* __restrict__ vnorm) {
-  const int v = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
-  if (v >= V) return;
-  render_vnormal_body(verts + (size_t)n * V * 3, faces, adj_ptr, adj_idx, V, F, vnorm + ((size_t)n * V + v) * 3, v);
-}
-__global__ __launch_bounds__(256) void render_vnormal_var_kernel(RndVarTab tab, const int* __restrict__ faces,
-                                                                 const int* __restrict__ adj_ptr, const int* __restrict__ adj_idx,
-                                                                 int V, int F, float* __restrict__ vnorm) {
-  const int v = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
-  if (v >= V) return;
-  render_vnormal_body(tab.m[n].verts, faces, adj_ptr, adj_idx, V, F, vnorm + ((size_t)n * V + v) * 3, v);
-}
-
-__global__ __launch_bounds__(256) void render_vnormal_scene_kernel(RndSceneTab tab, const int* __restrict__ faces,
-                                                                   const int* __restrict__ adj_ptr, const int* __restrict__ adj_idx,
-                                                                   int V, int F, float* __restrict__ vnorm) {
+__global__ __launch_bounds__(256) void render_vnormal_kernel(RndTab tab, const int* __restrict__ faces, const int* __restrict__ adj_ptr,
+                                                             const int* __restrict__ adj_idx, int V, int F, float* __restrict__ vnorm) {
   const int v = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
   if (v >= V) return;
   render_vnormal_body(tab.verts[n], faces, adj_ptr, adj_idx, V, F, vnorm + ((size_t)n * V + v) * 3, v);
@@ -198,29 +176,9 @@ __device__ __forceinline__ void render_face_setup_body(const float* __restrict__
   b[0] = bx;
   b[1] = by;
 }
-__global__ __launch_bounds__(256) void render_face_setup_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
-                                                                const float* __restrict__ cam, int V, int F, int H, int W,
-                                                                int* __restrict__ fcoord, int* __restrict__ fbox) {
-  const int f = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
-  if (f >= F) return;
-  const size_t g = (size_t)n * F + f;
-  render_face_setup_body(verts + (size_t)n * V * 3, faces, cam[4 * n], cam[4 * n + 1], cam[4 * n + 2], cam[4 * n + 3], V, H, W,
-                         fcoord + g * 6, fbox + 2 * g, f);
-}
-__global__ __launch_bounds__(256) void render_face_setup_var_kernel(RndVarTab tab, const int* __restrict__ faces,
-                                                                    const float* __restrict__ cam, int V, int F,
-                                                                    int* __restrict__ fcoord, int* __restrict__ fbox) {
-  const int f = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
-  if (f >= F) return;
-  const size_t g = (size_t)n * F + f;
-  render_face_setup_body(tab.m[n].verts, faces, cam[4 * n], cam[4 * n + 1], cam[4 * n + 2], cam[4 * n + 3], V, tab.m[n].H, tab.m[n].W,
-                         fcoord + g * 6, fbox + 2 * g, f);
-}
-
-// a mesh of a scene call is set up on its scene's frame size
-__global__ __launch_bounds__(256) void render_face_setup_scene_kernel(RndSceneTab tab, const int* __restrict__ faces,
-                                                                      const float* __restrict__ cam, int V, int F,
-                                                                      int* __restrict__ fcoord, int* __restrict__ fbox) {
+// a mesh is set up on its scene's frame size
+__global__ __launch_bounds__(256) void render_face_setup_kernel(RndTab tab, const int* __restrict__ faces, const float* __restrict__ cam,
+                                                                int V, int F, int* __restrict__ fcoord, int* __restrict__ fbox) {
   const int f = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
   if (f >= F) return;
   const size_t g = (size_t)n * F + f;
@@ -229,7 +187,7 @@ __global__ __launch_bounds__(256) void render_face_setup_scene_kernel(RndSceneTa
                          fcoord + g * 6, fbox + 2 * g, f);
 }
 
-// ---- pixel box of a whole mesh (ragged entry) -----------------------------------------------------------------------------------
+// ---- pixel box of a whole mesh (ragged and scene entries) ------------------------------------------------------------------------
 // One workgroup per mesh: the union of its faces' pixel boxes, reduced in LDS with integer min / max - deterministic, no atomics.
 // mbox[4 n ..] = xlo, xhi, ylo, yhi; a mesh with no drawn face keeps the empty box (xlo > xhi).
 __global__ __launch_bounds__(256) void render_mesh_box_kernel(const int* __restrict__ fbox, int F, int* __restrict__ mbox) {
@@ -396,180 +354,21 @@ __device__ __forceinline__ void render_chunk_nearest(const float* __restrict__ P
   // the entries of this chunk are overwritten two chunks on, behind the next barrier
 }
 
-// The 16 x 16 tile at (tx0, ty0) of ONE mesh: P its vertex rows, N its normals, C / B its faces' snapped corners and boxes, bg / out
-// (/ face_id / depth) its own H x W images.  skip (the same for the whole workgroup): no face of the mesh touches the tile - the
-// frame is copied and the face list is not streamed.
-__device__ __forceinline__ void render_tile_body(const float* __restrict__ P, const int* __restrict__ faces, const float* __restrict__ N,
-                                                 const int* __restrict__ C, const int* __restrict__ B, const uint8_t* __restrict__ bg,
-                                                 float cr, float cg, float cb, int F, int H, int W, int wide, uint8_t* __restrict__ out,
-                                                 int* __restrict__ face_id, float* __restrict__ depth, int tx0, int ty0, bool skip) {
-  __shared__ int s_xy[2][6][RND_CHUNK];
-  __shared__ int s_box[2][2][RND_CHUNK];
-  __shared__ float s_z[2][3][RND_CHUNK];
-  __shared__ int s_f[2][RND_CHUNK];
-  __shared__ unsigned s_cnt[3];
-  __shared__ __attribute__((aligned(16))) uint8_t s_px[RND_TILE][RND_TILE * 3];
-  const int t = threadIdx.x;
-  const int tx1 = rnd_min(tx0 + RND_TILE, W) - 1, ty1 = rnd_min(ty0 + RND_TILE, H) - 1;
-  const int lx = t & (RND_TILE - 1), ly = t >> 4;
-  const int i = tx0 + lx, j = ty0 + ly;
-  const bool live = i < W && j < H;
-  const int px = 256 * i + 128, py = 256 * j + 128;
-  render_frame_load(s_px, bg, H, W, wide, tx0, ty0, t, lx, ly, i, j, live);
-  if (t < 3) s_cnt[t] = 0;
-  __syncthreads();
-
-  float best = __uint_as_float(0x7f800000u);      // +inf
-  int best_f = -1;
-  const int nchunks = skip ? 0 : (F + RND_CHUNK - 1) / RND_CHUNK;
-  for (int c = 0; c < nchunks; ++c) {
-    render_chunk_nearest(P, faces, C, B, F, c, c, tx0, tx1, ty0, ty1, t, i, j, px, py, live, s_xy, s_box, s_z, s_f, s_cnt, best, best_f);
-  }
-
-  if (live && best_f >= 0) render_shade(P, faces, N, C, best_f, px, py, cr, cg, cb, &s_px[ly][3 * lx]);
-  if (live) {
-    if (face_id) face_id[(size_t)j * W + i] = best_f;
-    if (depth) depth[(size_t)j * W + i] = best_f >= 0 ? best : __uint_as_float(0x7f800000u);
-  }
-  __syncthreads();
-  render_frame_store(s_px, out, H, W, wide, tx0, ty0, t, lx, ly, i, j, live);
-}
-
-__global__ __launch_bounds__(256) void render_tile_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+// One workgroup per tile of a scene, on a flat grid over the prefix of the scenes' tile counts: workgroup -> (scene, tile) by a search
+// of the prefix.  Each mesh of a scene has its own weak-perspective camera: the Z of two people is measured about two pelvises and
+// cannot be compared, so there is NO depth test between meshes.  Within a mesh the nearest face wins (ties: the lower index), between
+// meshes the one listed later wins wherever it covers the pixel - what the chain  img = render(img, mesh_i)  over the list draws,
+// byte for byte.  The workgroup walks the scene's meshes from the last (on top) to the first: a mesh whose pixel box misses the tile
+// (use_box) is passed over, a pixel is decided by the first mesh it meets that covers it, a decided pixel makes no more coverage
+// tests, and the walk ends when every live pixel of the tile is decided.  The pixel is shaded once, at the end, with the winner's
+// vertex rows, normals and colour: colors[3 m ..], or (cr, cg, cb) for every mesh when colors is NULL (the uniform and ragged
+// entries pass one colour as scalars and allocate nothing).  depth (uniform entry only: its scenes share one H x W, scene k's map
+// lies at depth + k H W): the winning face's depth, +inf where nothing is drawn.
+__global__ __launch_bounds__(256) void render_tile_kernel(RndTab tab, int nscenes, const int* __restrict__ faces,
                                                           const float* __restrict__ vnorm, const int* __restrict__ fcoord,
-                                                          const int* __restrict__ fbox, const uint8_t* __restrict__ bg, float cr,
-                                                          float cg, float cb, int V, int F, int H, int W, int wide,
-                                                          uint8_t* __restrict__ out, int* __restrict__ face_id,
-                                                          float* __restrict__ depth) {
-  const int n = blockIdx.z;
-  const size_t img = (size_t)n * H * W;
-  render_tile_body(verts + (size_t)n * V * 3, faces, vnorm + (size_t)n * V * 3, fcoord + (size_t)n * F * 6, fbox + (size_t)n * F * 2,
-                   bg ? bg + img * 3 : nullptr, cr, cg, cb, F, H, W, wide, out + img * 3, face_id ? face_id + img : nullptr,
-                   depth ? depth + img : nullptr, blockIdx.x * RND_TILE, blockIdx.y * RND_TILE, false);
-}
-// The ragged form: a flat grid over the prefix of the meshes' tile counts; workgroup -> (mesh, tile) by a search of the prefix.  A
-// tile outside its mesh's pixel box (use_box) copies the frame and leaves.
-__global__ __launch_bounds__(256) void render_tile_var_kernel(RndVarTab tab, int nmesh, const int* __restrict__ faces,
-                                                              const float* __restrict__ vnorm, const int* __restrict__ fcoord,
-                                                              const int* __restrict__ fbox, const int* __restrict__ mbox, float cr,
-                                                              float cg, float cb, int V, int F, int use_box) {
-  const int bid = (int)blockIdx.x;
-  int lo = 0, hi = nmesh;                       // the mesh n with tile0[n] <= bid < tile0[n + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (tab.tile0[mid] <= bid) lo = mid;
-    else hi = mid;
-  }
-  const int n = lo;
-  const RndMesh m = tab.m[n];
-  const int tw = (m.W + RND_TILE - 1) / RND_TILE, local = bid - tab.tile0[n];
-  const int ty = local / tw, tx = local - ty * tw;
-  const int tx0 = tx * RND_TILE, ty0 = ty * RND_TILE;
-  bool skip = false;
-  if (use_box) {
-    const int xlo = mbox[4 * n], xhi = mbox[4 * n + 1], ylo = mbox[4 * n + 2], yhi = mbox[4 * n + 3];
-    skip = xlo > xhi || xlo > tx0 + RND_TILE - 1 || xhi < tx0 || ylo > ty0 + RND_TILE - 1 || yhi < ty0;
-  }
-  const int wide = m.W % 16 == 0 && ((uintptr_t)m.out & 15) == 0 && ((uintptr_t)m.bg & 15) == 0;
-  render_tile_body(m.verts, faces, vnorm + (size_t)n * V * 3, fcoord + (size_t)n * F * 6, fbox + (size_t)n * F * 2, m.bg, cr, cg, cb,
-                   F, m.H, m.W, wide, m.out, nullptr, nullptr, tx0, ty0, skip);
-}
-
-// scratch: vertex normals [N][V][3] fp32 (first, so a caller can read them back), snapped corners [N][F][6] int32, boxes [N][F][2] int32
-extern "C" size_t dyb_render_workspace_bytes(int N, int V, int F) {
-  if (N <= 0 || V <= 0 || F <= 0) return 0;
-  return rnd_align((size_t)N * V * 3 * sizeof(float)) + rnd_align((size_t)N * F * 6 * sizeof(int)) +
-         rnd_align((size_t)N * F * 2 * sizeof(int));
-}
-
-extern "C" int dyb_render_meshes(const float* verts, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
-                                 const uint8_t* background, float col_r, float col_g, float col_b, uint8_t* out, int* face_id,
-                                 float* depth, int N, int V, int F, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
-  DYB_REQUIRE(verts && faces && adj_ptr && adj_idx && cam && out && ws, DYB_ERR_ARG);
-  DYB_REQUIRE(N > 0 && V > 0 && F > 0 && H > 0 && W > 0, DYB_ERR_ARG);
-  DYB_REQUIRE(N <= RND_MAX_N && H <= RND_MAX_DIM && W <= RND_MAX_DIM, DYB_ERR_UNSUPPORTED);
-  DYB_REQUIRE(F <= (1 << 28) && V <= (1 << 28), DYB_ERR_UNSUPPORTED);                  // 3 F and 3 V stay inside int
-  DYB_REQUIRE(ws_bytes >= dyb_render_workspace_bytes(N, V, F), DYB_ERR_WORKSPACE);
-  char* w = reinterpret_cast<char*>(ws);
-  float* vnorm = reinterpret_cast<float*>(w);
-  w += rnd_align((size_t)N * V * 3 * sizeof(float));
-  int* fcoord = reinterpret_cast<int*>(w);
-  w += rnd_align((size_t)N * F * 6 * sizeof(int));
-  int* fbox = reinterpret_cast<int*>(w);
-  hipLaunchKernelGGL(render_vnormal_kernel, dim3(dyb_cdiv(V, 256), 1, N), dim3(256), 0, st, verts, faces, adj_ptr, adj_idx, V, F, vnorm);
-  DYB_CHECK_LAUNCH();
-  hipLaunchKernelGGL(render_face_setup_kernel, dim3(dyb_cdiv(F, 256), 1, N), dim3(256), 0, st, verts, faces, cam, V, F, H, W, fcoord, fbox);
-  DYB_CHECK_LAUNCH();
-  const int wide = W % 16 == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)background & 15) == 0;
-  hipLaunchKernelGGL(render_tile_kernel, dim3(dyb_cdiv(W, RND_TILE), dyb_cdiv(H, RND_TILE), N), dim3(256), 0, st, verts, faces,
-                     (const float*)vnorm, (const int*)fcoord, (const int*)fbox, background, col_r, col_g, col_b, V, F, H, W, wide, out,
-                     face_id, depth);
-  DYB_CHECK_LAUNCH();
-  return DYB_OK;
-}
-
-// ---- the ragged entry: every mesh with its own frame size and pointers ----------------------------------------------------------
-// scratch: as above, then the meshes' pixel boxes [N][4] int32
-extern "C" size_t dyb_render_var_workspace_bytes(int N, int V, int F) {
-  if (N <= 0 || V <= 0 || F <= 0) return 0;
-  return dyb_render_workspace_bytes(N, V, F) + rnd_align((size_t)N * 4 * sizeof(int));
-}
-
-// desc: HOST table of N entries (copied into the launches' kernel arguments: free to reuse when the call returns).  flags bit 0:
-// leave the per-mesh pixel box out (every tile streams the face list, as the uniform entry does; same bytes - for measurements).
-extern "C" int dyb_render_meshes_var(const dyb_render_desc* desc, const int* faces, const int* adj_ptr, const int* adj_idx,
-                                     const float* cam, float col_r, float col_g, float col_b, int N, int V, int F, int flags, void* ws,
-                                     size_t ws_bytes, hipStream_t st) {
-  DYB_REQUIRE(desc && faces && adj_ptr && adj_idx && cam && ws, DYB_ERR_ARG);
-  DYB_REQUIRE(N > 0 && V > 0 && F > 0, DYB_ERR_ARG);
-  DYB_REQUIRE(N <= RND_MAX_N, DYB_ERR_UNSUPPORTED);
-  DYB_REQUIRE(F <= (1 << 28) && V <= (1 << 28), DYB_ERR_UNSUPPORTED);
-  RndVarTab tab{};
-  long long tiles = 0;
-  for (int n = 0; n < N; ++n) {
-    const dyb_render_desc& d = desc[n];
-    DYB_REQUIRE(d.verts && d.out && d.H > 0 && d.W > 0, DYB_ERR_ARG);
-    DYB_REQUIRE(d.H <= RND_MAX_DIM && d.W <= RND_MAX_DIM, DYB_ERR_UNSUPPORTED);
-    tab.m[n] = RndMesh{d.verts, d.background, d.out, d.H, d.W};
-    tab.tile0[n] = (int)tiles;
-    tiles += (long long)dyb_cdiv(d.W, RND_TILE) * dyb_cdiv(d.H, RND_TILE);      // <= 64 * 256 * 256: inside int and a 1-D grid
-  }
-  for (int n = N; n <= RND_MAX_N; ++n) tab.tile0[n] = (int)tiles;
-  DYB_REQUIRE(ws_bytes >= dyb_render_var_workspace_bytes(N, V, F), DYB_ERR_WORKSPACE);
-  char* w = reinterpret_cast<char*>(ws);
-  float* vnorm = reinterpret_cast<float*>(w);
-  w += rnd_align((size_t)N * V * 3 * sizeof(float));
-  int* fcoord = reinterpret_cast<int*>(w);
-  w += rnd_align((size_t)N * F * 6 * sizeof(int));
-  int* fbox = reinterpret_cast<int*>(w);
-  w += rnd_align((size_t)N * F * 2 * sizeof(int));
-  int* mbox = reinterpret_cast<int*>(w);
-  const int use_box = (flags & 1) ? 0 : 1;
-  hipLaunchKernelGGL(render_vnormal_var_kernel, dim3(dyb_cdiv(V, 256), 1, N), dim3(256), 0, st, tab, faces, adj_ptr, adj_idx, V, F, vnorm);
-  DYB_CHECK_LAUNCH();
-  hipLaunchKernelGGL(render_face_setup_var_kernel, dim3(dyb_cdiv(F, 256), 1, N), dim3(256), 0, st, tab, faces, cam, V, F, fcoord, fbox);
-  DYB_CHECK_LAUNCH();
-  if (use_box) {
-    hipLaunchKernelGGL(render_mesh_box_kernel, dim3(N), dim3(256), 0, st, (const int*)fbox, F, mbox);
-    DYB_CHECK_LAUNCH();
-  }
-  hipLaunchKernelGGL(render_tile_var_kernel, dim3((unsigned)tiles), dim3(256), 0, st, tab, N, faces, (const float*)vnorm,
-                     (const int*)fcoord, (const int*)fbox, (const int*)mbox, col_r, col_g, col_b, V, F, use_box);
-  DYB_CHECK_LAUNCH();
-  return DYB_OK;
-}
-
-// ---- the scene entry: several meshes over ONE frame, in painter order ------------------------------------------------------------
-// Each mesh of a scene has its own weak-perspective camera: the Z of two people is measured about two pelvises and cannot be
-// compared, so there is NO depth test between meshes.  Within a mesh the nearest face wins (ties: the lower index), between meshes
-// the one listed later wins wherever it covers the pixel - what the chain  img = render(img, mesh_i)  over the list draws, byte for
-// byte.  One workgroup per tile of a scene walks the scene's meshes from the last (on top) to the first: a pixel is decided by the
-// first mesh it meets that covers it, a decided pixel makes no more coverage tests, and the walk ends when every live pixel of the
-// tile is decided.  The pixel is shaded once, at the end, with the winner's vertex rows, normals and colour.
-__global__ __launch_bounds__(256) void render_tile_scene_kernel(RndSceneTab tab, int nscenes, const int* __restrict__ faces,
-                                                                const float* __restrict__ vnorm, const int* __restrict__ fcoord,
-                                                                const int* __restrict__ fbox, const int* __restrict__ mbox,
-                                                                const float* __restrict__ colors, int V, int F, int use_box) {
+                                                          const int* __restrict__ fbox, const int* __restrict__ mbox,
+                                                          const float* __restrict__ colors, float* __restrict__ depth, float cr,
+                                                          float cg, float cb, int V, int F, int use_box) {
   __shared__ int s_xy[2][6][RND_CHUNK];
   __shared__ int s_box[2][2][RND_CHUNK];
   __shared__ float s_z[2][3][RND_CHUNK];
@@ -589,6 +388,8 @@ __global__ __launch_bounds__(256) void render_tile_scene_kernel(RndSceneTab tab,
   const int tw = (W + RND_TILE - 1) / RND_TILE, local = bid - tab.tile0[lo];
   const int tyi = local / tw, txi = local - tyi * tw;
   const int tx0 = txi * RND_TILE, ty0 = tyi * RND_TILE;
+  // decided per scene; for the uniform entry one decision for the call, as its images lie n H W 3 bytes apart: a multiple of 16
+  // whenever W is
   const int wide = W % 16 == 0 && ((uintptr_t)sc.out & 15) == 0 && ((uintptr_t)sc.bg & 15) == 0;
   const int t = threadIdx.x;
   const int tx1 = rnd_min(tx0 + RND_TILE, W) - 1, ty1 = rnd_min(ty0 + RND_TILE, H) - 1;
@@ -603,6 +404,7 @@ __global__ __launch_bounds__(256) void render_tile_scene_kernel(RndSceneTab tab,
   __syncthreads();
 
   int win_m = -1, win_f = -1;                   // the mesh (index in the call's list) and the face this pixel shows
+  float win_d = __uint_as_float(0x7f800000u);   // ... and its depth there; +inf: nothing
   const int nchunks = (F + RND_CHUNK - 1) / RND_CHUNK;
   int g = 0;                                    // chunks streamed so far, over all meshes
   for (int m = (int)sc.m1 - 1; m >= (int)sc.m0; --m) {
@@ -619,11 +421,15 @@ __global__ __launch_bounds__(256) void render_tile_scene_kernel(RndSceneTab tab,
     for (int c = 0; c < nchunks; ++c, ++g)
       render_chunk_nearest(P, faces, C, B, F, c, g, tx0, tx1, ty0, ty1, t, i, j, px, py, live && win_m < 0, s_xy, s_box, s_z, s_f, s_cnt,
                            best, best_f);
-    if (live && win_m < 0 && best_f >= 0) {
+    const bool won = live && win_m < 0 && best_f >= 0;
+    if (won) {
       win_m = m;
       win_f = best_f;
-      atomicAdd(&s_decided, 1u);
+      win_d = best;
     }
+    // the bottom mesh of the scene (the only one of a uniform or ragged picture): no walk is left to end, nobody needs the count
+    if (m == (int)sc.m0) break;
+    if (won) atomicAdd(&s_decided, 1u);
     // read behind the barrier: one value for the whole workgroup.  The next addition to it lies behind a barrier of the next mesh's
     // first chunk, which no thread passes before all have read it here.
     __syncthreads();
@@ -632,21 +438,117 @@ __global__ __launch_bounds__(256) void render_tile_scene_kernel(RndSceneTab tab,
 
   if (live && win_m >= 0)
     render_shade(tab.verts[win_m], faces, vnorm + (size_t)win_m * V * 3, fcoord + (size_t)win_m * F * 6, win_f, px, py,
-                 colors[3 * win_m], colors[3 * win_m + 1], colors[3 * win_m + 2], &s_px[ly][3 * lx]);
+                 colors ? colors[3 * win_m] : cr, colors ? colors[3 * win_m + 1] : cg, colors ? colors[3 * win_m + 2] : cb,
+                 &s_px[ly][3 * lx]);
   if (live) {
     if (sc.mesh_id) sc.mesh_id[(size_t)j * W + i] = win_m >= 0 ? win_m - (int)sc.m0 : -1;
     if (sc.face_id) sc.face_id[(size_t)j * W + i] = win_f;
+    if (depth) depth[((size_t)lo * H + j) * W + i] = win_d;
   }
   __syncthreads();
   render_frame_store(s_px, sc.out, H, W, wide, tx0, ty0, t, lx, ly, i, j, live);
 }
 
-// scratch: that of the ragged entry for nmeshes meshes (normals, snapped corners, face boxes, mesh boxes); none without a mesh
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+// scratch: vertex normals [N][V][3] fp32 (first, so a caller can read them back), snapped corners [N][F][6] int32, boxes [N][F][2] int32
+extern "C" size_t dyb_render_workspace_bytes(int N, int V, int F) {
+  if (N <= 0 || V <= 0 || F <= 0) return 0;
+  return rnd_align((size_t)N * V * 3 * sizeof(float)) + rnd_align((size_t)N * F * 6 * sizeof(int)) +
+         rnd_align((size_t)N * F * 2 * sizeof(int));
+}
+// scratch of the ragged entry: as above, then the meshes' pixel boxes [N][4] int32
+extern "C" size_t dyb_render_var_workspace_bytes(int N, int V, int F) {
+  if (N <= 0 || V <= 0 || F <= 0) return 0;
+  return dyb_render_workspace_bytes(N, V, F) + rnd_align((size_t)N * 4 * sizeof(int));
+}
+// scratch of the scene entry: that of the ragged entry for nmeshes meshes; none without a mesh
 extern "C" size_t dyb_render_scenes_workspace_bytes(int nmeshes, int V, int F) { return dyb_render_var_workspace_bytes(nmeshes, V, F); }
 
+// The launches of a checked call: the table's tile prefix is filled in, the workspace carved (the one statement of its layout: the
+// workspace_bytes functions above count these parts) and the kernels issued - normals, face set-up and, with use_box, the mesh boxes
+// for the M meshes of the list, then the tiles of the nscenes scenes.  use_box = 0: the workspace need not hold the mesh boxes.
+static int render_launch(RndTab& tab, int nscenes, int M, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
+                         const float* colors, float cr, float cg, float cb, float* depth, int V, int F, int use_box, void* ws,
+                         hipStream_t st) {
+  long long tiles = 0;
+  for (int k = 0; k <= RND_MAX_N; ++k) {
+    tab.tile0[k] = (int)tiles;
+    if (k < nscenes) tiles += (long long)dyb_cdiv(tab.s[k].W, RND_TILE) * dyb_cdiv(tab.s[k].H, RND_TILE);      // <= 64 * 256 * 256: inside int and a 1-D grid
+  }
+  char* w = reinterpret_cast<char*>(ws);
+  float* vnorm = reinterpret_cast<float*>(w);
+  w += rnd_align((size_t)M * V * 3 * sizeof(float));
+  int* fcoord = reinterpret_cast<int*>(w);
+  w += rnd_align((size_t)M * F * 6 * sizeof(int));
+  int* fbox = reinterpret_cast<int*>(w);
+  w += rnd_align((size_t)M * F * 2 * sizeof(int));
+  int* mbox = use_box ? reinterpret_cast<int*>(w) : nullptr;
+  if (M > 0) {
+    hipLaunchKernelGGL(render_vnormal_kernel, dim3(dyb_cdiv(V, 256), 1, M), dim3(256), 0, st, tab, faces, adj_ptr, adj_idx, V, F, vnorm);
+    DYB_CHECK_LAUNCH();
+    hipLaunchKernelGGL(render_face_setup_kernel, dim3(dyb_cdiv(F, 256), 1, M), dim3(256), 0, st, tab, faces, cam, V, F, fcoord, fbox);
+    DYB_CHECK_LAUNCH();
+    if (use_box) {
+      hipLaunchKernelGGL(render_mesh_box_kernel, dim3(M), dim3(256), 0, st, (const int*)fbox, F, mbox);
+      DYB_CHECK_LAUNCH();
+    }
+  }
+  hipLaunchKernelGGL(render_tile_kernel, dim3((unsigned)tiles), dim3(256), 0, st, tab, nscenes, faces, (const float*)vnorm,
+                     (const int*)fcoord, (const int*)fbox, (const int*)mbox, colors, depth, cr, cg, cb, V, F, use_box);
+  DYB_CHECK_LAUNCH();
+  return DYB_OK;
+}
+
+// ---- the uniform entry: N meshes, one frame size, strided images -----------------------------------------------------------------
+// No pixel box: three launches, and the workspace has no room for the mesh boxes.
+extern "C" int dyb_render_meshes(const float* verts, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
+                                 const uint8_t* background, float col_r, float col_g, float col_b, uint8_t* out, int* face_id,
+                                 float* depth, int N, int V, int F, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
+  DYB_REQUIRE(verts && faces && adj_ptr && adj_idx && cam && out && ws, DYB_ERR_ARG);
+  DYB_REQUIRE(N > 0 && V > 0 && F > 0 && H > 0 && W > 0, DYB_ERR_ARG);
+  DYB_REQUIRE(N <= RND_MAX_N && H <= RND_MAX_DIM && W <= RND_MAX_DIM, DYB_ERR_UNSUPPORTED);
+  DYB_REQUIRE(F <= (1 << 28) && V <= (1 << 28), DYB_ERR_UNSUPPORTED);                  // 3 F and 3 V stay inside int
+  DYB_REQUIRE(ws_bytes >= dyb_render_workspace_bytes(N, V, F), DYB_ERR_WORKSPACE);
+  RndTab tab{};
+  const size_t img = (size_t)H * W;
+  for (int n = 0; n < N; ++n) {
+    tab.s[n] = RndScene{background ? background + n * img * 3 : nullptr, out + n * img * 3, nullptr, face_id ? face_id + n * img : nullptr,
+                        (unsigned short)H, (unsigned short)W, (unsigned char)n, (unsigned char)(n + 1)};
+    tab.verts[n] = verts + (size_t)n * V * 3;
+    tab.scene_of[n] = (unsigned char)n;
+  }
+  return render_launch(tab, N, N, faces, adj_ptr, adj_idx, cam, nullptr, col_r, col_g, col_b, depth, V, F, 0, ws, st);
+}
+
+// ---- the ragged entry: every mesh with its own frame size and pointers ----------------------------------------------------------
+// desc: HOST table of N entries (copied into the launches' kernel arguments: free to reuse when the call returns).  flags bit 0:
+// leave the per-mesh pixel box out (every tile streams the face list, as the uniform entry does; same bytes - for measurements).
+extern "C" int dyb_render_meshes_var(const dyb_render_desc* desc, const int* faces, const int* adj_ptr, const int* adj_idx,
+                                     const float* cam, float col_r, float col_g, float col_b, int N, int V, int F, int flags, void* ws,
+                                     size_t ws_bytes, hipStream_t st) {
+  DYB_REQUIRE(desc && faces && adj_ptr && adj_idx && cam && ws, DYB_ERR_ARG);
+  DYB_REQUIRE(N > 0 && V > 0 && F > 0, DYB_ERR_ARG);
+  DYB_REQUIRE(N <= RND_MAX_N, DYB_ERR_UNSUPPORTED);
+  DYB_REQUIRE(F <= (1 << 28) && V <= (1 << 28), DYB_ERR_UNSUPPORTED);
+  RndTab tab{};
+  for (int n = 0; n < N; ++n) {
+    const dyb_render_desc& d = desc[n];
+    DYB_REQUIRE(d.verts && d.out && d.H > 0 && d.W > 0, DYB_ERR_ARG);
+    DYB_REQUIRE(d.H <= RND_MAX_DIM && d.W <= RND_MAX_DIM, DYB_ERR_UNSUPPORTED);
+    tab.s[n] = RndScene{d.background, d.out, nullptr, nullptr, (unsigned short)d.H, (unsigned short)d.W, (unsigned char)n,
+                        (unsigned char)(n + 1)};
+    tab.verts[n] = d.verts;
+    tab.scene_of[n] = (unsigned char)n;
+  }
+  DYB_REQUIRE(ws_bytes >= dyb_render_var_workspace_bytes(N, V, F), DYB_ERR_WORKSPACE);
+  return render_launch(tab, N, N, faces, adj_ptr, adj_idx, cam, nullptr, col_r, col_g, col_b, nullptr, V, F, (flags & 1) ? 0 : 1, ws, st);
+}
+
+// ---- the scene entry: several meshes over ONE frame, in painter order ------------------------------------------------------------
 // scenes: HOST table of nscenes entries; mesh_verts: HOST table of nmeshes device pointers; mesh_scene: HOST table, the scene of
 // each mesh (it must agree with the scenes' ranges, which must tile 0 .. nmeshes in order).  Both are copied into the launches'
-// kernel arguments.  flags bit 0: leave the per-mesh pixel boxes out (same bytes - for measurements).
+// kernel arguments.  flags bit 0: leave the per-mesh pixel boxes out (same bytes - for measurements).  Without a mesh (ws may be
+// NULL) only the tiles are launched: they copy the frames.
 extern "C" int dyb_render_scenes(const dyb_render_scene* scenes, int nscenes, const float* const* mesh_verts, const int* mesh_scene,
                                  const float* cam, const float* colors, const int* faces, const int* adj_ptr, const int* adj_idx,
                                  int nmeshes, int V, int F, int flags, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -655,8 +557,7 @@ extern "C" int dyb_render_scenes(const dyb_render_scene* scenes, int nscenes, co
   DYB_REQUIRE(nmeshes == 0 || (mesh_verts && mesh_scene && cam && colors && ws), DYB_ERR_ARG);
   DYB_REQUIRE(nscenes <= RND_MAX_N && nmeshes <= RND_MAX_N, DYB_ERR_UNSUPPORTED);
   DYB_REQUIRE(F <= (1 << 28) && V <= (1 << 28), DYB_ERR_UNSUPPORTED);
-  RndSceneTab tab{};
-  long long tiles = 0;
+  RndTab tab{};
   int next = 0;
   for (int k = 0; k < nscenes; ++k) {
     const dyb_render_scene& d = scenes[k];
@@ -671,36 +572,9 @@ extern "C" int dyb_render_scenes(const dyb_render_scene* scenes, int nscenes, co
       tab.verts[m] = mesh_verts[m];
       tab.scene_of[m] = (unsigned char)k;
     }
-    tab.tile0[k] = (int)tiles;
-    tiles += (long long)dyb_cdiv(d.W, RND_TILE) * dyb_cdiv(d.H, RND_TILE);      // <= 64 * 256 * 256: inside int and a 1-D grid
   }
   DYB_REQUIRE(next == nmeshes, DYB_ERR_ARG);
-  for (int k = nscenes; k <= RND_MAX_N; ++k) tab.tile0[k] = (int)tiles;
   DYB_REQUIRE(ws_bytes >= dyb_render_scenes_workspace_bytes(nmeshes, V, F), DYB_ERR_WORKSPACE);
-  const int M = nmeshes;
-  char* w = reinterpret_cast<char*>(ws);
-  float* vnorm = reinterpret_cast<float*>(w);
-  w += rnd_align((size_t)M * V * 3 * sizeof(float));
-  int* fcoord = reinterpret_cast<int*>(w);
-  w += rnd_align((size_t)M * F * 6 * sizeof(int));
-  int* fbox = reinterpret_cast<int*>(w);
-  w += rnd_align((size_t)M * F * 2 * sizeof(int));
-  int* mbox = reinterpret_cast<int*>(w);
-  const int use_box = (flags & 1) ? 0 : 1;
-  if (M > 0) {
-    hipLaunchKernelGGL(render_vnormal_scene_kernel, dim3(dyb_cdiv(V, 256), 1, M), dim3(256), 0, st, tab, faces, adj_ptr, adj_idx, V, F,
-                       vnorm);
-    DYB_CHECK_LAUNCH();
-    hipLaunchKernelGGL(render_face_setup_scene_kernel, dim3(dyb_cdiv(F, 256), 1, M), dim3(256), 0, st, tab, faces, cam, V, F, fcoord,
-                       fbox);
-    DYB_CHECK_LAUNCH();
-    if (use_box) {
-      hipLaunchKernelGGL(render_mesh_box_kernel, dim3(M), dim3(256), 0, st, (const int*)fbox, F, mbox);
-      DYB_CHECK_LAUNCH();
-    }
-  }
-  hipLaunchKernelGGL(render_tile_scene_kernel, dim3((unsigned)tiles), dim3(256), 0, st, tab, nscenes, faces, (const float*)vnorm,
-                     (const int*)fcoord, (const int*)fbox, (const int*)mbox, colors, V, F, use_box);
-  DYB_CHECK_LAUNCH();
-  return DYB_OK;
+  // with no mesh the colours may be NULL; the tile kernel then never reads a colour
+  return render_launch(tab, nscenes, nmeshes, faces, adj_ptr, adj_idx, cam, colors, 0.f, 0.f, 0.f, nullptr, V, F, (flags & 1) ? 0 : 1, ws, st);
 }

@@ -101,6 +101,9 @@ class Renderer:
         self._ws: Dict[tuple, torch.Tensor] = {}
 
     def _adjacency(self, V: int, dev: torch.device):
+        """(faces, vertex -> face ptr, idx) on dev for meshes of V vertices."""
+        if V < self.min_verts:
+            raise ValueError(f"faces index vertex {self.min_verts - 1} but the mesh has {V} vertices")
         key = (V, str(dev))
         hit = self._tables.get(key)
         if hit is None:
@@ -115,6 +118,38 @@ class Renderer:
         if self.device is not None:
             return self.device
         return torch.device("cuda" if torch.cuda.is_available() else "cpu")
+
+    def _workspace(self, dev: torch.device, nbytes: int) -> torch.Tensor:
+        """The scratch of a call: one buffer per (device, stream), grown when a call needs more."""
+        key = (str(dev), torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = self._ws[key] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        return ws
+
+    def _frame(self, bg, dev: torch.device, over: str):
+        """A frame (uint8 RGB (H, W, 3)) or None (black at `resolution`) -> (contiguous tensor on dev or None, H, W)."""
+        if bg is None:
+            W, H = self.resolution
+        else:
+            bg = torch.as_tensor(bg).to(dev)
+            if bg.dtype != torch.uint8 or bg.dim() != 3 or bg.shape[2] != 3:
+                raise ValueError(f"the frame under the {over} must be uint8 RGB (H, W, 3)")
+            bg = bg.contiguous()
+            H, W = int(bg.shape[0]), int(bg.shape[1])
+        if not (0 < H <= MAX_DIM and 0 < W <= MAX_DIM):
+            raise ValueError(f"frame size {(H, W)} outside 1 .. {MAX_DIM}")
+        return bg, H, W
+
+    @staticmethod
+    def _row(v, V: int, dev: torch.device, message: str) -> torch.Tensor:
+        """One mesh's vertices as a contiguous fp32 (V, 3) row on dev: the tensor itself where it already is one."""
+        v = torch.as_tensor(v).detach()
+        if v.dtype != torch.float32 or not v.is_contiguous() or v.device != dev:
+            v = v.to(dev, torch.float32).contiguous()
+        if tuple(v.shape) != (V, 3):
+            raise ValueError(message)
+        return v
 
     def rasterize(self, verts, cam, img=None, color: Sequence[float] = DEFAULT_COLOR, return_normals=False):
         """-> (image uint8 (N, H, W, 3), face_id int32 (N, H, W), -1 where nothing is drawn, depth fp32 (N, H, W), +inf there);
@@ -132,8 +167,8 @@ class Renderer:
         v, c = v.contiguous(), c.contiguous()
         N, V = int(v.shape[0]), int(v.shape[1])
         W, H = self.resolution
-        if V < self.min_verts:
-            raise ValueError(f"faces index vertex {self.min_verts - 1} but the mesh has {V} vertices")
+        faces, ptr, idx = self._adjacency(V, dev)
+        F = int(faces.shape[0])
         bg = None
         if img is not None:
             bg = torch.as_tensor(img).to(dev)
@@ -145,13 +180,7 @@ class Renderer:
                 raise ValueError(f"frame shape {tuple(bg.shape)} does not match (N, H, W, 3) = {(N, H, W, 3)}")
             bg = bg.contiguous()
         lib = _lib.load()
-        faces, ptr, idx = self._adjacency(V, dev)
-        F = int(faces.shape[0])
-        nbytes = int(lib.dyb_render_workspace_bytes(N, V, F))
-        sid = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
-        ws = self._ws.get((str(dev), sid))
-        if ws is None or ws.numel() < nbytes:
-            ws = self._ws[(str(dev), sid)] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        ws = self._workspace(dev, int(lib.dyb_render_workspace_bytes(N, V, F)))
         out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=dev)
         fid = torch.empty(N, H, W, dtype=torch.int32, device=dev)
         depth = torch.empty(N, H, W, dtype=torch.float32, device=dev)
@@ -182,39 +211,19 @@ class Renderer:
         dev = verts_rows[0].device
         c = torch.as_tensor(cams).detach().to(dev, torch.float32).reshape(N, 4).contiguous()
         V = int(verts_rows[0].shape[0])
-        if V < self.min_verts:
-            raise ValueError(f"faces index vertex {self.min_verts - 1} but the mesh has {V} vertices")
-        lib = _lib.load()
         faces, ptr, idx = self._adjacency(V, dev)
         F = int(faces.shape[0])
         desc = (RenderDesc * N)()
         keep, outs = [], []
         for i in range(N):
-            v = verts_rows[i].detach()
-            if v.dtype != torch.float32 or not v.is_contiguous() or v.device != dev:
-                v = v.to(dev, torch.float32).contiguous()
-            if tuple(v.shape) != (V, 3):
-                raise ValueError("verts_rows must be (V, 3) each, with one V")
-            bg = frames[i]
-            if bg is None:
-                W, H = self.resolution
-            else:
-                bg = torch.as_tensor(bg).to(dev)
-                if bg.dtype != torch.uint8 or bg.dim() != 3 or bg.shape[2] != 3:
-                    raise ValueError("the frame under the mesh must be uint8 RGB (H, W, 3)")
-                bg = bg.contiguous()
-                H, W = int(bg.shape[0]), int(bg.shape[1])
-            if not (0 < H <= MAX_DIM and 0 < W <= MAX_DIM):
-                raise ValueError(f"frame size {(H, W)} outside 1 .. {MAX_DIM}")
+            v = self._row(verts_rows[i], V, dev, "verts_rows must be (V, 3) each, with one V")
+            bg, H, W = self._frame(frames[i], dev, "mesh")
             out = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
             desc[i] = RenderDesc(v.data_ptr(), bg.data_ptr() if bg is not None else None, out.data_ptr(), H, W)
             keep += [v, bg]
             outs.append(out)
-        nbytes = int(lib.dyb_render_var_workspace_bytes(N, V, F))
-        sid = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
-        ws = self._ws.get((str(dev), sid))
-        if ws is None or ws.numel() < nbytes:
-            ws = self._ws[(str(dev), sid)] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        lib = _lib.load()
+        ws = self._workspace(dev, int(lib.dyb_render_var_workspace_bytes(N, V, F)))
         col = [float(x) for x in color]
         check(lib.dyb_render_meshes_var(ctypes.cast(desc, ctypes.c_void_p), faces.data_ptr(), ptr.data_ptr(), idx.data_ptr(), c.data_ptr(),
                                         col[0], col[1], col[2], N, V, F, 0 if box else 1, ws.data_ptr(), ws.numel(), stream_of(c)),
@@ -256,9 +265,6 @@ class Renderer:
         dev = self._device_of(*frames, *(m[0] for m in meshes))
         M = len(meshes)
         V = int(meshes[0][0].shape[0]) if M else self.min_verts
-        if V < self.min_verts:
-            raise ValueError(f"faces index vertex {self.min_verts - 1} but the mesh has {V} vertices")
-        lib = _lib.load()
         faces, ptr, idx = self._adjacency(V, dev)
         F = int(faces.shape[0])
         desc = (RenderScene * len(scenes))()
@@ -266,25 +272,12 @@ class Renderer:
         keep, pics, mids, fids, cams, cols = [], [], [], [], [], []
         at = 0
         for k, (bg, sc) in enumerate(zip(frames, scenes)):
-            if bg is None:
-                W, H = self.resolution
-            else:
-                bg = torch.as_tensor(bg).to(dev)
-                if bg.dtype != torch.uint8 or bg.dim() != 3 or bg.shape[2] != 3:
-                    raise ValueError("the frame under the meshes must be uint8 RGB (H, W, 3)")
-                bg = bg.contiguous()
-                H, W = int(bg.shape[0]), int(bg.shape[1])
-            if not (0 < H <= MAX_DIM and 0 < W <= MAX_DIM):
-                raise ValueError(f"frame size {(H, W)} outside 1 .. {MAX_DIM}")
+            bg, H, W = self._frame(bg, dev, "meshes")
             out = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
             mid = torch.empty(H, W, dtype=torch.int32, device=dev) if ids else None
             fid = torch.empty(H, W, dtype=torch.int32, device=dev) if ids else None
             for v, cam, col in sc:
-                v = torch.as_tensor(v).detach()
-                if v.dtype != torch.float32 or not v.is_contiguous() or v.device != dev:
-                    v = v.to(dev, torch.float32).contiguous()
-                if tuple(v.shape) != (V, 3):
-                    raise ValueError("the meshes of a call must be (V, 3) each, with one V")
+                v = self._row(v, V, dev, "the meshes of a call must be (V, 3) each, with one V")
                 vptr[at], mscene[at] = v.data_ptr(), k
                 keep.append(v)
                 cams.append(torch.as_tensor(cam).detach().to(dev, torch.float32).reshape(4))
@@ -299,11 +292,8 @@ class Renderer:
                 fids.append(fid)
         cam = torch.stack(cams).contiguous() if M else None
         colors = torch.tensor(cols, dtype=torch.float32).reshape(M, 3).to(dev) if M else None
-        nbytes = int(lib.dyb_render_scenes_workspace_bytes(M, V, F))
-        sid = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
-        ws = self._ws.get((str(dev), sid))
-        if ws is None or ws.numel() < nbytes:
-            ws = self._ws[(str(dev), sid)] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        lib = _lib.load()
+        ws = self._workspace(dev, int(lib.dyb_render_scenes_workspace_bytes(M, V, F)))
         check(lib.dyb_render_scenes(ctypes.cast(desc, ctypes.c_void_p), len(scenes), ctypes.cast(vptr, ctypes.c_void_p),
                                     ctypes.cast(mscene, ctypes.c_void_p), cam.data_ptr() if M else None, colors.data_ptr() if M else None,
                                     faces.data_ptr(), ptr.data_ptr(), idx.data_ptr(), M, V, F, 0, ws.data_ptr(), ws.numel(), stream_of(ws)),

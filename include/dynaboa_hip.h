@@ -516,7 +516,7 @@ int dyb_render_meshes(const float* verts, const int* faces, const int* adj_ptr, 
  * background [H][W][3] uint8 (device) or NULL (black), out [H][W][3] uint8 (device), H, W <= 4096.  The table and the prefix of
  * the meshes' tile counts travel as kernel arguments: no allocation, no copy, no host wait; the table may be reused when the
  * call returns.  cam [N][4] stays a device array.  Mesh i equals, byte for byte, dyb_render_meshes called alone with that mesh,
- * H_i, W_i (the kernels share their bodies).  One workgroup per mesh first reduces the faces' pixel boxes to the mesh's own box
+ * H_i, W_i (the same kernels: a mesh of this call is a scene of one mesh).  One workgroup per mesh first reduces the faces' pixel boxes to the mesh's own box
  * (integer min / max in LDS: deterministic); the tile grid is flat over all meshes and a tile outside its mesh's box copies the
  * frame without streaming the face list (flags bit 0 set: no box, every tile streams - same bytes, for measurements; other bits 0).
  * A mesh with no drawn face has an empty box: its picture is the frame.  DYB_ERR_ARG: NULL table / verts / out, non-positive size;
@@ -536,7 +536,7 @@ int dyb_render_meshes_var(const dyb_render_desc* desc, const int* faces, const i
  * one call.  Every mesh has its own weak-perspective camera, so depths of different meshes are not comparable and there is NO
  * depth test between meshes - the painter rule instead: within a mesh the nearest face wins (ties: lower face index), between
  * meshes the one listed LATER wins wherever it covers a pixel, whatever its Z.  A scene equals, byte for byte, the chain
- * img = frame; for i in its range: img = dyb_render_meshes(mesh i over img, colour i) - drawn in one pass: one workgroup per tile
+ * img = frame; for i in its range: img = dyb_render_meshes(mesh i over img, colour i) - the same kernels, in one pass: one workgroup per tile
  * walks the scene's meshes from the last to the first, skips a mesh whose pixel box misses the tile, stops testing a pixel once a
  * mesh has claimed it, leaves when every pixel of the tile is decided and shades each pixel once; the frame is read and written once.
  * scenes: HOST table of nscenes entries - background [H][W][3] uint8 (device) or NULL (black), out [H][W][3] uint8 (device),

@@ -10,47 +10,14 @@ the integer test and lie within 1e-6 max|Z| of the winner - are capped at 0.1 % 
 (emulator) for every mesh used here: icosphere 80 / 320 faces at 64x64, 70x45 and the three-camera batches: 0 of 431 ... 2023
 covered pixels; synthetic SMPL at 224x224, two poses: first 2000 faces 0 of 9785 / 7329, all 13 776 faces 0 of 12 862 / 8926 ; on
 an MI355X the same counts, and 0 of 155 856 for the 1920x1080 case, which exists there only (every case prints its count, `-s`)."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import render_ref as RR
-
-_EMU = {}
-
-
-@pytest.fixture
-def emu_lib():
-    """The emulator build bound for the duration of ONE test (the GPU cases of this file must see the real library)."""
-    from emu.build_emu import build
-    from dynaboa_amd import _abi, _lib
-    if "lib" not in _EMU:
-        _EMU["lib"] = _abi.bind(ctypes.CDLL(build()))
-    saved = _lib._lib
-    _lib.use_library(_EMU["lib"])
-    yield _EMU["lib"]
-    _lib._lib = saved
-
-
-@pytest.fixture(params=["emu", pytest.param("gpu", marks=pytest.mark.gpu)])
-def dev(request):
-    if request.param == "emu":
-        request.getfixturevalue("emu_lib")
-        return "cpu"
-    return "cuda:0"
-
+from render_cases import ZOFF, dev, emu_lib, icosphere, rasterize, smpl_case, sphere_case      # noqa: F401 (fixtures)
 
 # ---------------------------------------------------------------------------- helpers
-def rasterize(dev, verts, faces, cam, H, W, bg=None, color=(1.0, 1.0, 0.9)):
-    from dynaboa_amd.render import Renderer
-    r = Renderer(resolution=(W, H), faces=faces, device=dev)
-    out = r.rasterize(torch.as_tensor(np.asarray(verts, np.float32)).to(dev), torch.as_tensor(np.asarray(cam, np.float32)).to(dev),
-                      None if bg is None else torch.as_tensor(bg).to(dev), color, return_normals=True)
-    return tuple(o.cpu().numpy() for o in out)
-
-
 UNIT16 = (1.0, 1.0, 0.0, 0.0)          # on a 16 x 16 image: u = 8 (1 + X), exact for the coordinates used below
 
 
@@ -68,33 +35,6 @@ def right_tri_mask(x0, y0, L, n=16):
     """Integer x0, y0, L: left and top edges own the centres on them (none lie there), the hypotenuse runs down and does not."""
     j, i = np.mgrid[0:n, 0:n]
     return (i >= x0) & (j >= y0) & (i + j + 1 < x0 + y0 + L)
-
-
-def icosphere(level):
-    t = (1.0 + 5.0 ** 0.5) / 2.0
-    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
-    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
-         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
-    v = [np.array(p, np.float64) / np.linalg.norm(p) for p in v]
-    for _ in range(level):
-        mid, nf = {}, []
-
-        def m(a, b):
-            k = (min(a, b), max(a, b))
-            if k not in mid:
-                p = v[a] + v[b]
-                v.append(p / np.linalg.norm(p))
-                mid[k] = len(v) - 1
-            return mid[k]
-        for a, b, c in f:
-            ab, bc, ca = m(a, b), m(b, c), m(c, a)
-            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
-        f = nf
-    v, f = np.array(v), np.array(f, np.int64)
-    n = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
-    inward = (n * v[f].mean(1)).sum(1) < 0
-    f[inward] = f[inward][:, ::-1]               # outward normals: the side facing the camera (towards -Z) is the front
-    return v.astype(np.float32), f
 
 
 def compare(got, ref, verts, tag=""):
@@ -211,7 +151,6 @@ def test_known_unordered_depth_and_far_corners(dev):
 
 # ---------------------------------------------------------------------------- against render_ref
 _REF = {}
-ZOFF = 2.0          # the test meshes sit in front of Z = 0, so that "1e-5 relative" on the depth means what it says at every pixel
 
 
 def ref_of(key, verts, faces, cam, H, W, bg, color):
@@ -219,17 +158,6 @@ def ref_of(key, verts, faces, cam, H, W, bg, color):
     if key not in _REF:
         _REF[key] = [RR.render(verts[k], faces, cam[k], H, W, None if bg is None else bg[k], color) for k in range(len(verts))]
     return _REF[key]
-
-
-def sphere_case(level, H, W, ncam):
-    v, f = icosphere(level)
-    rng = np.random.default_rng(100 * level + H + ncam)
-    R = np.linalg.qr(rng.normal(size=(3, 3)))[0]
-    cams = np.array([[0.8, 0.8, 0.05, -0.1], [0.5, 0.9, 0.7, 0.3], [1.6, 1.3, -0.4, 0.6]], np.float32)[:ncam]
-    verts = np.stack([(v @ (R if k % 2 == 0 else R.T)).astype(np.float32) * (1.0 - 0.2 * k) for k in range(ncam)])
-    verts[:, :, 2] += ZOFF
-    bg = rng.integers(0, 256, (ncam, H, W, 3), dtype=np.uint8)
-    return verts, f, cams, bg
 
 
 @pytest.mark.parametrize("level,H,W,ncam", [(1, 64, 64, 1), (2, 64, 64, 1), (1, 45, 70, 1), (2, 45, 70, 1), (1, 64, 64, 3), (2, 48, 40, 3)])
@@ -262,24 +190,6 @@ def test_replica_indexing(dev):
         i1, f1, d1, n1 = rasterize(dev, verts[k:k + 1], f, cams[k:k + 1], 37, 50, bg=bg[k:k + 1])
         assert i1[0].tobytes() == img[k].tobytes() and f1[0].tobytes() == fid[k].tobytes() and d1[0].tobytes() == depth[k].tobytes()
         assert n1[0].tobytes() == vn[k].tobytes()
-
-
-def smpl_case(dev, smpl_tabs, nfaces):
-    from dynaboa_amd.smpl import SMPL
-    g = torch.Generator().manual_seed(5)
-    pose, betas = torch.randn(2, 72, generator=g) * 0.3, torch.randn(2, 10, generator=g) * 0.5
-    smpl = SMPL(tables=smpl_tabs).to(dev)
-    with torch.no_grad():
-        verts = smpl(betas=betas.to(dev), body_pose=pose[:, 3:].to(dev), global_orient=pose[:, :3].to(dev)).vertices.cpu().numpy()
-    faces = np.asarray(smpl_tabs["faces"])[:nfaces]
-    cams = []
-    for k in range(2):
-        lo, hi = verts[k, :, :2].min(0), verts[k, :, :2].max(0)
-        s = 1.7 / float((hi - lo).max())
-        cams.append([s, s * 0.9, -(lo[0] + hi[0]) / 2 + 0.02 * k, -(lo[1] + hi[1]) / 2])
-    verts = verts.astype(np.float32)
-    verts[:, :, 2] += ZOFF + np.abs(verts[:, :, 2]).max()
-    return verts, faces, np.array(cams, np.float32)
 
 
 def check_smpl(dev, smpl_tabs, nfaces):

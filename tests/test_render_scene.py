@@ -12,49 +12,13 @@ import pytest
 import torch
 
 import scene_ref as SR
-from test_render import icosphere, smpl_case
+from render_cases import (COLORS, T, dev, draw, emu_lib, frame, front_mesh, icosphere, smpl_case, sphere, spread_rows,      # noqa: F401 (fixtures)
+                          three_scenes)
 
-_EMU = {}
 _REF = {}
-COLORS = [(205 / 255.0, 129 / 255.0, 98 / 255.0), (0.2, 0.9, 0.4), (0.35, 0.45, 1.0)]
-
-
-@pytest.fixture
-def emu_lib():
-    from emu.build_emu import build
-    from dynaboa_amd import _abi, _lib
-    if "lib" not in _EMU:
-        _EMU["lib"] = _abi.bind(ctypes.CDLL(build()))
-    saved = _lib._lib
-    _lib.use_library(_EMU["lib"])
-    yield _EMU["lib"]
-    _lib._lib = saved
-
-
-@pytest.fixture(params=["emu", pytest.param("gpu", marks=pytest.mark.gpu)])
-def dev(request):
-    if request.param == "emu":
-        request.getfixturevalue("emu_lib")
-        return "cpu"
-    return "cuda:0"
 
 
 # ---------------------------------------------------------------------------- helpers
-def T(a, dev, dt=np.float32):
-    return torch.as_tensor(np.asarray(a, dt)).to(dev)
-
-
-def sphere(level, radius=1.0, z=3.0):
-    v, f = icosphere(level)
-    v = (v * radius).astype(np.float32)
-    v[:, 2] += z
-    return v, f
-
-
-def frame(H, W, seed=0):
-    return np.random.default_rng(seed).integers(0, 256, (H, W, 3), dtype=np.uint8)
-
-
 def chain(dev, faces, meshes, H, W, bg):
     """img = frame; for mesh in order: img = Renderer.render(img, mesh) - the oracle for the pictures."""
     from dynaboa_amd.render import Renderer
@@ -65,21 +29,6 @@ def chain(dev, faces, meshes, H, W, bg):
     for v, cam, col in meshes:
         img = r.render(img, T(v, dev), T(cam, dev), color=col)
     return img.cpu().numpy()
-
-
-def draw(dev, faces, frames, scenes, resolution=(16, 16), rows=None):
-    """One render_scenes call with ids.  rows: device views to use as the vertex rows (else the arrays are uploaded)."""
-    from dynaboa_amd.render import Renderer
-    r = Renderer(resolution=resolution, faces=faces, device=dev)
-    k = 0
-    sc = []
-    for s in scenes:
-        sc.append([])
-        for v, cam, col in s:
-            sc[-1].append((rows[k] if rows is not None else T(v, dev), T(cam, dev), col))
-            k += 1
-    pics, mids, fids = r.render_scenes([None if b is None else T(b, dev, np.uint8) for b in frames], sc, return_ids=True)
-    return [p.cpu().numpy() for p in pics], [m.cpu().numpy() for m in mids], [f.cpu().numpy() for f in fids]
 
 
 def ref_ids(key, meshes, faces, H, W):
@@ -143,23 +92,10 @@ def test_three_scenes_one_call(dev):
     """Sizes (33, 20), (16, 16), (48, 64) (H, W), mesh counts 1, 3 and 0, the vertex rows views at unequal strides inside one
     NaN-filled buffer, the second frame None (black)."""
     from dynaboa_amd.render import Renderer
-    v, faces = sphere(1)
-    V = len(v)
-    meshes = [(v, [0.7, 0.6, 0.1, -0.1], COLORS[0]),
-              (v * np.float32(0.7), [0.8, 0.8, -0.4, 0.0], COLORS[1]), (v * np.float32(0.9), [0.6, 0.7, 0.3, 0.2], COLORS[2]),
-              (v * np.float32(0.5), [0.9, 0.9, 0.0, -0.3], COLORS[0])]
-    gaps = [5 + 7 * i for i in range(4)]
-    buf = torch.full((sum(gaps) + 4 * V * 3 + 3,), float("nan"), dtype=torch.float32, device=dev)
-    rows, at = [], 0
-    for m, g in zip(meshes, gaps):
-        at += g
-        buf[at:at + V * 3] = T(m[0], dev).reshape(-1)
-        rows.append(buf[at:at + V * 3].view(V, 3))
-        at += V * 3
-    bgs = [frame(33, 20, seed=2), None, frame(48, 64, seed=3)]
-    scenes = [meshes[:1], meshes[1:], []]
+    faces, meshes, bgs, scenes, sizes = three_scenes()
+    rows = spread_rows(dev, [m[0] for m in meshes])
     pics, mids, fids = draw(dev, faces, bgs, scenes, resolution=(16, 16), rows=rows)
-    for k, (H, W) in enumerate([(33, 20), (16, 16), (48, 64)]):
+    for k, (H, W) in enumerate(sizes):
         check_scene(dev, ("three scenes", k), faces, scenes[k], H, W, bgs[k], (pics[k], mids[k], fids[k]))
     assert (pics[0] != bgs[0]).any() and (mids[1] == 2).sum() > 10 and (mids[1] == 1).sum() > 10
     assert pics[2].tobytes() == bgs[2].tobytes() and np.all(mids[2] == -1) and np.all(fids[2] == -1)      # the empty scene: its frame
@@ -189,11 +125,7 @@ def test_mesh_off_the_image_and_nan_rows_leave_no_trace(dev):
 def test_front_mesh_decides_its_tiles(dev, front):
     """32 x 32 (four tiles).  The last listed sphere covers the whole picture (every tile leaves the walk after one mesh), or all of
     the two left tiles and a part of the right ones (the left tiles leave, the right ones go on to the mesh beneath)."""
-    v, faces = sphere(2)
-    under = (v, [0.7, 0.7, 0.1, -0.1], COLORS[1])
-    # whole: radius 2.2 half pictures about the centre; left: radius 24 px about (0, 16) - the far corners of the left tiles lie at 21.9
-    top = (v, [2.2, 2.2, 0.0, 0.0], COLORS[0]) if front == "whole" else (v, [1.5, 1.5, -1.0 / 1.5, 0.0], COLORS[0])
-    bg = frame(32, 32, seed=5)
+    faces, (under, top), bg = front_mesh(front)
     pics, mids, fids = draw(dev, faces, [bg], [[under, top]])
     _, mid = check_scene(dev, ("front", front), faces, [under, top], 32, 32, bg, (pics[0], mids[0], fids[0]))
     if front == "whole":

@@ -13,50 +13,10 @@ import numpy as np
 import pytest
 import torch
 
-from test_render import icosphere, smpl_case
-
-_EMU = {}
-COLOR = (205 / 255.0, 129 / 255.0, 98 / 255.0)
-
-
-@pytest.fixture
-def emu_lib():
-    from emu.build_emu import build
-    from dynaboa_amd import _abi, _lib
-    if "lib" not in _EMU:
-        _EMU["lib"] = _abi.bind(ctypes.CDLL(build()))
-    saved = _lib._lib
-    _lib.use_library(_EMU["lib"])
-    yield _EMU["lib"]
-    _lib._lib = saved
-
-
-@pytest.fixture(params=["emu", pytest.param("gpu", marks=pytest.mark.gpu)])
-def dev(request):
-    if request.param == "emu":
-        request.getfixturevalue("emu_lib")
-        return "cpu"
-    return "cuda:0"
-
+from render_cases import (COLOR, backgrounds, corner_tile, dev, emu_lib, icosphere, ragged, shifted, smpl_case, sphere_set,      # noqa: F401 (fixtures)
+                          three_spheres_three_sizes)
 
 # ---------------------------------------------------------------------------- helpers
-def sphere_set():
-    """-> (level-1 sphere in the level-2 table, level-2 sphere, faces of level 2)."""
-    v1, f1 = icosphere(1)
-    v2, f2 = icosphere(2)
-    assert np.array_equal(v2[:len(v1)], v1)
-    flat = v2.copy()
-    edges = {(min(a, b), max(a, b)) for tri in f1 for a, b in ((tri[0], tri[1]), (tri[1], tri[2]), (tri[2], tri[0]))}
-    placed = 0
-    for a, b in sorted(edges):
-        mid = (v1[a].astype(np.float64) + v1[b]) / 2
-        k = int(np.argmin(np.linalg.norm(v2[len(v1):] - mid / np.linalg.norm(mid), axis=1))) + len(v1)
-        flat[k] = mid.astype(np.float32)
-        placed += 1
-    assert placed == len(v2) - len(v1) == 120
-    return flat, v2, f2
-
-
 def uniform(dev, faces, verts, cam, bg):
     """dyb_render_meshes alone with this mesh at the frame's own size."""
     from dynaboa_amd.render import Renderer
@@ -65,43 +25,11 @@ def uniform(dev, faces, verts, cam, bg):
     return r.render(torch.as_tensor(bg).to(dev), torch.as_tensor(verts).to(dev), torch.as_tensor(cam).to(dev), color=COLOR).cpu().numpy()
 
 
-def ragged(dev, faces, meshes, cams, bgs, spread=True, box=True):
-    """One ragged call; the vertex rows sit at unequal strides inside one larger buffer (spread)."""
-    from dynaboa_amd.render import Renderer
-    V = meshes[0].shape[0]
-    gaps = [5 + 7 * i for i in range(len(meshes))] if spread else [0] * len(meshes)
-    buf = torch.full((sum(gaps) + len(meshes) * V * 3 + 3,), float("nan"), dtype=torch.float32, device=dev)
-    rows, at = [], 0
-    for m, g in zip(meshes, gaps):
-        at += g
-        buf[at:at + V * 3] = torch.as_tensor(np.asarray(m, np.float32)).reshape(-1).to(dev)
-        rows.append(buf[at:at + V * 3].view(V, 3))
-        at += V * 3
-    r = Renderer(resolution=(16, 16), faces=faces, device=dev)
-    outs = r.render_many([torch.as_tensor(b).to(dev) for b in bgs], rows, torch.as_tensor(np.asarray(cams, np.float32)).to(dev), color=COLOR,
-                        box=box)
-    return [o.cpu().numpy() for o in outs]
-
-
-def backgrounds(sizes, seed=0):
-    rng = np.random.default_rng(seed)
-    return [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in sizes]
-
-
-def shifted(v, z=3.0):
-    v = np.array(v, np.float32)
-    v[:, 2] += z
-    return v
-
-
 # ---------------------------------------------------------------------------- the contract
 def test_three_spheres_three_frame_sizes_equal_uniform_calls(dev):
     """Levels 1, 2, 1 over 64 x 64 (16-byte rows: the `wide` path), 45 x 70 and 48 x 40 (H x W; neither width a multiple of 16),
     random frames, three cameras, one call."""
-    flat, round2, faces = sphere_set()
-    meshes = [shifted(flat), shifted(round2), shifted(flat * 0.8)]
-    bgs = backgrounds([(64, 64), (45, 70), (48, 40)])
-    cams = [[0.8, 0.8, 0.05, -0.1], [0.5, 0.75, -0.3, 0.2], [0.9, 0.7, 0.4, 0.35]]
+    faces, meshes, cams, bgs = three_spheres_three_sizes()
     got = ragged(dev, faces, meshes, cams, bgs)
     nobox = ragged(dev, faces, meshes, cams, bgs, box=False)          # flags bit 0: no per-mesh box, the same bytes
     assert [g.tobytes() for g in got] == [g.tobytes() for g in nobox]
@@ -125,12 +53,9 @@ def test_mesh_off_its_frame_gives_back_the_frame(dev):
 def test_mesh_on_one_corner_tile_only(dev):
     """A small sphere inside the top-left 16 x 16 tile of a 48 x 40 frame: the mesh's pixel box ends inside tile (0, 0), every other
     tile of the frame lies outside it and takes the skip path - both sides of the box edge in one picture."""
-    _, round2, faces = sphere_set()
-    bg = backgrounds([(48, 40)], seed=2)[0]
-    # u = 20 (1 + sx (X + tx)), v = 24 (1 + sy (Y + ty)): centre at pixel (7, 8), radius 5 pixels
-    cam = [0.25, 5.0 / 24.0, -0.65 / 0.25, -(2.0 / 3.0) / (5.0 / 24.0)]
-    got = ragged(dev, faces, [shifted(round2)], [cam], [bg])[0]
-    assert got.tobytes() == uniform(dev, faces, shifted(round2), cam, bg).tobytes()
+    faces, mesh, cam, bg = corner_tile()
+    got = ragged(dev, faces, [mesh], [cam], [bg])[0]
+    assert got.tobytes() == uniform(dev, faces, mesh, cam, bg).tobytes()
     drawn = (got != bg).any(-1)
     assert drawn[:16, :16].sum() > 40 and not drawn[16:].any() and not drawn[:, 16:].any()
 

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
-from test_render import icosphere
+from render_cases import icosphere
 
 SEQ = "vid"
 W, H = 64, 48
