@@ -69,8 +69,15 @@ class BaseAdaptor:
             if self.bundle is None:
                 # the exemplar set retrieval() draws from (reference base_adaptor.py:55)
                 from . import datasets as D
-                self.h36m_dataset = D.SourceDataset('data/retrieval_res/h36m_random_sample_center_10_10.pt',
+                self.h36m_dataset = D.SourceDataset(self.H36M_SAMPLE_FILE,
                                                     img_dir=getattr(options, "h36m_root", None) or D.H36M_ROOT, device=self.device)
+                if getattr(options, "exemplar_bank", 0):
+                    # --exemplar_bank 1: the whole set preprocessed once and resident on the device (exemplar_bank.py; one bank per
+                    # (files, device), shared by the adaptors of a replica group); retrieval() then follows the bank's draw rule
+                    from .exemplar_bank import ExemplarBank
+                    self.exemplar_bank = ExemplarBank.from_tree(self.H36M_SAMPLE_FILE, self.H36M_CLUSTER_FILE, self.h36m_dataset.img_dir,
+                                                                self.device)
+                    self._bank_draw, self._bank_last_pick = 0, None
         self.set_model_optim()
         if options.use_meanteacher:
             self.set_teacher()
@@ -168,14 +175,34 @@ class BaseAdaptor:
         self.joint_mapper_gt = list(constants.J24_TO_J14)
 
     # ------------------------------------------------------------------ retrieval (base_adaptor.py:74-96)
+    H36M_SAMPLE_FILE = 'data/retrieval_res/h36m_random_sample_center_10_10.pt'                       # reference base_adaptor.py:55
+    H36M_CLUSTER_FILE = "data/retrieval_res/cluster_res_random_sample_center_10_10_potocol2.pt"      # reference base_adaptor.py:76
+
     def load_h36_cluster_res(self):
         """reference base_adaptor.py:74-80: cluster centres of the base model's Human3.6M features + member indices."""
         self.centers = None
         if self.bundle is None:
             import joblib
-            res = self.h36m_cluster_res = joblib.load("data/retrieval_res/cluster_res_random_sample_center_10_10_potocol2.pt")
+            res = self.h36m_cluster_res = joblib.load(self.H36M_CLUSTER_FILE)
             self.centers = torch.from_numpy(np.asarray(res["centers"])).float().to(self.device)
             self.index = res["index"]
+
+    # the exemplars the latest level used: a plain attribute on the autograd and callback routes; with the bank on the device the stepper
+    # leaves a recipe (its latest logged pick) and the dict is built when somebody reads it
+    @property
+    def _last_h36m(self):
+        make = self.__dict__.pop("_last_h36m_make", None)
+        if make is not None:
+            self.__dict__["_last_h36m_value"] = make()
+        return self.__dict__.get("_last_h36m_value")
+
+    @_last_h36m.setter
+    def _last_h36m(self, batch):
+        self.__dict__.pop("_last_h36m_make", None)
+        self.__dict__["_last_h36m_value"] = batch
+
+    def defer_last_h36m(self, make):
+        self.__dict__["_last_h36m_make"] = make
 
     def get_h36m_data(self, indice):
         return dict(self.h36m_dataset[indice])
@@ -183,7 +210,18 @@ class BaseAdaptor:
     def retrieval(self, feature):
         """reference base_adaptor.py:82-96: nearest cluster by cosine distance of features[5] (the pooled 2048-vector) to
         the centres, `sample_num` members drawn with the seeded `random` module, their items concatenated along dim 0.
-        The cluster index is the one host synchronisation of the level (the reference's `.item()`)."""
+        The cluster index is the one host synchronisation of the level (the reference's `.item()`).
+        With --exemplar_bank 1 (no bundle) the nearest centre (ties: lowest index) and the member come from the bank's kernels: draw
+        number `_bank_draw` of this adaptor under seed options.seed (exemplar_bank.py) - the rule the native stepper applies on the
+        device, so the autograd path, the callback route and the device route pick the same exemplars."""
+        bank = getattr(self, "exemplar_bank", None)
+        if bank is not None and self.bundle is None:
+            if self.options.sample_num != 1:
+                raise ValueError("--exemplar_bank 1 draws one exemplar per retrieval (sample_num 1)")
+            batch, picks = bank.select(feature, [self._bank_draw], self.options.seed)
+            self._bank_draw += 1
+            self._bank_last_pick = picks[0]
+            return batch
         if self.bundle is not None:
             dev_fn = getattr(self.bundle, "exemplars_device", None)
             if dev_fn is not None:            # synthetic exemplars: resident on the device, one generation per step for all sequences

@@ -126,6 +126,11 @@ parser.add_argument('--native_results', type=int, default=0, choices=[0, 1],
                          'stepper keeps each frame\'s last final inference in a result ring on the device, the overlay of a step\'s frames '
                          'is drawn from there by one ragged launch and the dump is written from there; 0 (default): both take the run '
                          'to the torch.autograd composition')
+parser.add_argument('--exemplar_bank', type=int, default=0, choices=[0, 1],
+                    help='1 (with a real data tree): the retrieval set is preprocessed once and kept resident on the device (602 KB per '
+                         'exemplar); the nearest cluster and the member are picked by HIP kernels from a counter-based generator seeded '
+                         'with --seed (same distribution as the reference\'s random.sample, not the same samples) and the native stepper '
+                         'retrieves inside the level - no host callback, parallel passes stay on; 0 (default): the reference\'s host retrieval')
 parser.add_argument('--eval_lower', type=int, default=1, choices=[0, 1],
                     help='run inference() after every inner step like the reference (:142)')
 

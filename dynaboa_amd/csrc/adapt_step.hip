@@ -56,6 +56,11 @@ int dyb_aux_loss_terms_kp(int, int, int, float, const float*, const float*, int,
                           const float*, int, const float*, int, const float*, const float*, const float*, const float*, const float*,
                           const float*, float*, float*, float*, float*, float*, float*, float*, int, hipStream_t);
 int dyb_hmr_feature_info(const void*, int, long long*, int*, int*);
+size_t dyb_retrieve_workspace_bytes(int, int, int);
+int dyb_retrieve_select(const float*, size_t, const int*, int, const float*, const float*, int, const int*, const int*, int, int,
+                        const unsigned long long*, unsigned long long, int, int*, size_t, int, int, int, void*, size_t, hipStream_t);
+int dyb_exemplar_gather(const int*, size_t, int, const int*, int, const unsigned long long*, const float*, const float*, const float*,
+                        const float*, const float*, int, float* const*, const size_t*, hipStream_t);
 }
 int dyb_adam_step_rep(float*, const float*, float*, float*, float, float, const float*, const float*, float, size_t, hipStream_t);   // optim.hip
 int dyb_adam_step_rep3(float*, const float*, const float*, const float*, float*, float*, float, float, const float*, const float*, float, size_t,
@@ -297,6 +302,19 @@ struct Stepper {
   int (*retrieve)(void*, int, const void**) = nullptr;
   int (*retrieve_rep)(void*, int, int, const void**) = nullptr;     // replica groups: (user, level, physical replica, out[5])
   void* retrieve_user = nullptr;
+  // Exemplar bank (retrieval.hip): the whole retrieval set resident on the device (caller's tables).  Bound (all pointers set,
+  // "bank_on_device" 1), a level with a labelled term selects each replica's nearest cluster from its own pooled feature on the chain,
+  // draws a member and gathers that exemplar into the replica's exemplar staging - no host callback, so the parallel passes stay on.
+  // The draw index is host state: bank_draw[r] counts the labelled levels issued for physical replica r (the dynamic gate is a host
+  // poll, so the host knows), handed to the kernels as arguments and logged in bank_picks row (draw mod bank_pick_capacity).
+  const float *bank_img = nullptr, *bank_kp = nullptr, *bank_pose = nullptr, *bank_betas = nullptr, *bank_pose3d = nullptr;
+  const float *bank_centers = nullptr, *bank_inv_norm = nullptr;
+  const int *bank_member_ptr = nullptr, *bank_member_idx = nullptr;
+  int* bank_picks = nullptr;
+  int bank_items = 0, bank_clusters = 0, bank_members = 0, bank_pick_capacity = 0, bank_on_device = 1;
+  unsigned long long bank_seed = 0;
+  unsigned long long bank_draw[DYB_MAX_REPLICAS] = {};
+  char* retr_ws = nullptr;            // select partials (replica 0's blob: sized for every replica of the handle)
   FeatCosArgs fca{};
   float gate_seq = 0.f;
   Pass lvl0{}, ex{}, hist{}, teach{};
@@ -311,7 +329,8 @@ struct Stepper {
   int nactive = 0;                    // 0 = all
   long long adam_t_rep[DYB_MAX_REPLICAS] = {};   // Adam steps taken, per replica (they differ once the dynamic loop or ragged streams do)
   size_t blob = 0;                    // workspace bytes of ONE replica
-  float* in_stage[12] = {};           // staging of the frame inputs, in IN_* order (replica 0; nrep > 1 only)
+  float* in_stage[12] = {};           // staging of the frame inputs, in IN_* order (replica 0): all kinds for nrep > 1; one sequence: only
+                                      // the exemplar kinds, and only with an exemplar bank set before the workspace is sized
   double lr = 3e-6, beta1 = 0.5, beta2 = 0.9, eps = 1e-8, fastlr = 8e-6, w2d = 10.0, wshape = 2e-6, wpose = 1e-4;
   long long adam_t = 0;
   // caller-owned state and tables (device pointers)
@@ -365,7 +384,7 @@ struct Stepper {
   int par_passes = 1, par_max_replicas = DYB_MAX_REPLICAS;   // measured up to 32 per launch: 16: 290 -> 316, 32: 362 -> 377 frames/s (s30)
   hipStream_t par_stream[2] = {nullptr, nullptr};                                 // history pass | exemplar pass.  (A third stream for the teacher's
   // forward was measured and removed: 75.7 - 76.9 frames/s against 89.4 - 92.3 with two, profiles/r05_sessions.txt s25.)
-  hipEvent_t par_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // fork | hist fwd | hist head grads | hist bwd | label term | exemplar bwd | error-path tails of the two pass streams
+  hipEvent_t par_ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // fork | hist fwd | hist head grads | hist bwd | label term | exemplar bwd | error-path tails of the two pass streams | bank select
   bool out_in_main = false;        // where the latest final inference lives (dyb_stepper_output): fin, or main after an odd number of shared steps
   int share_dyn_fwd = 1;           // dynamic loop: an extra step's upper level reuses the previous step's final inference as its forward
   hipEvent_t e_upd = nullptr;
@@ -425,6 +444,8 @@ struct HostTimer {
 };
 
 static size_t a64(size_t v) { return (v + 63) & ~(size_t)63; }
+#define BANK_MAX_CHUNKS 256           // select partials per replica: the centres go to at most this many workgroups per replica
+static bool bank_bound(const Stepper& S) { return S.bank_img && S.bank_on_device; }
 static const char* opt_env(const char* name) { return name ? getenv(name) : nullptr; }
 
 // carve (or, with base == nullptr, size) the workspace
@@ -505,7 +526,15 @@ static size_t carve(Stepper& S, char* base) {
       S.in_stage[10] = take_f(B * 10);
       S.in_stage[11] = take_f(B * 24 * 4);
     }
+  } else if (S.full && S.bank_img) {             // one sequence: only the exemplar bank's gather writes staged inputs
+    S.in_stage[7] = take_f(B * 3 * (size_t)S.H * S.W);
+    S.in_stage[8] = take_f(B * NJ * 3);
+    S.in_stage[9] = take_f(B * 72);
+    S.in_stage[10] = take_f(B * 10);
+    S.in_stage[11] = take_f(B * 24 * 4);
   }
+  // (the bank's pointers are set before the workspace is sized; without a bank the layout is what it was)
+  S.retr_ws = (S.full && S.bank_img) ? take_b(dyb_retrieve_workspace_bytes(S.nrep, BANK_MAX_CHUNKS, 1)) : nullptr;
   return off;
 }
 
@@ -553,7 +582,7 @@ extern "C" void dyb_stepper_destroy(void* stepper) {
   if (S->gates.ev[0]) (void)hipEventDestroy(S->gates.ev[0]);
   if (S->gates.ev[1]) (void)hipEventDestroy(S->gates.ev[1]);
   if (S->gates.mid) (void)hipEventDestroy(S->gates.mid);
-  for (int i = 0; i < 8; ++i) if (S->par_ev[i]) (void)hipEventDestroy(S->par_ev[i]);
+  for (int i = 0; i < 9; ++i) if (S->par_ev[i]) (void)hipEventDestroy(S->par_ev[i]);
   for (int i = 0; i < 2; ++i) if (S->par_stream[i]) (void)hipStreamDestroy(S->par_stream[i]);
   delete S;
 }
@@ -582,6 +611,12 @@ extern "C" int dyb_stepper_set_i(void* stepper, const char* key, long long v) {
     S->adam_t = 0;                                    // "adam_step" reports the largest count among the handle's replicas
     for (int q = 0; q < S->nrep || q <= r; ++q)
       if (S->adam_t_rep[q] > S->adam_t) S->adam_t = S->adam_t_rep[q];
+  }
+  else if (k == "bank_seed") S->bank_seed = (unsigned long long)v;
+  else if (k.compare(0, 10, "bank_draw_") == 0) {     // "bank_draw_<replica>": labelled levels issued so far = the next draw index
+    const int r = atoi(k.c_str() + 10);
+    DYB_REQUIRE(r >= 0 && r < DYB_MAX_REPLICAS, DYB_ERR_ARG);
+    S->bank_draw[r] = (unsigned long long)v;
   }
   else if (k == "drop_seed") S->drop_seed = (unsigned long long)v;
   else if (k == "drop_offset") { S->drop_off = (unsigned long long)v; S->drop_used = 0; }
@@ -645,6 +680,11 @@ extern "C" long long dyb_stepper_get_i(const void* stepper, const char* key) {
   if (k.compare(0, 10, "adam_step_") == 0) {          // "adam_step_<replica>"
     const int r = atoi(k.c_str() + 10);
     return (r >= 0 && r < S->nrep) ? S->adam_t_rep[r] : -1;
+  }
+  if (k == "bank_seed") return (long long)S->bank_seed;
+  if (k.compare(0, 10, "bank_draw_") == 0) {
+    const int r = atoi(k.c_str() + 10);
+    return (r >= 0 && r < S->nrep) ? (long long)S->bank_draw[r] : -1;
   }
   if (k == "drop_used") return S->drop_used;
   if (k == "result_floats") return (long long)S->B * RESULT_FLOATS;
@@ -729,6 +769,15 @@ static int check_ready(const Stepper& S) {
   DYB_REQUIRE(S.inner_step >= 0 && S.inner_step <= 16 && S.n_iter >= 1 && S.n_iter <= 3, DYB_ERR_UNSUPPORTED);
   DYB_REQUIRE(!S.results || S.result_capacity > 0, DYB_ERR_ARG);
   DYB_REQUIRE(S.kp_set == 0 || S.kp_set == 1, DYB_ERR_ARG);       // (the setter stores any value: refused here, before the first launch)
+  if (bank_bound(S)) {
+    // a bank and a retrieval callback are two answers to one question: refused rather than ranked
+    DYB_REQUIRE(!S.retrieve && !S.retrieve_rep, DYB_ERR_ARG);
+    DYB_REQUIRE(S.full && S.B == 1, DYB_ERR_UNSUPPORTED);         // feature-driven retrieval is batch 1
+    DYB_REQUIRE(S.bank_kp && S.bank_pose && S.bank_betas && S.bank_pose3d && S.bank_centers && S.bank_inv_norm && S.bank_member_ptr &&
+                S.bank_member_idx && S.bank_picks, DYB_ERR_ARG);
+    DYB_REQUIRE(S.bank_items > 0 && S.bank_clusters > 0 && S.bank_members > 0 && S.bank_pick_capacity > 0, DYB_ERR_ARG);
+    DYB_REQUIRE(S.retr_ws && S.in_stage[7], DYB_ERR_WORKSPACE);          // "bank_img" was set after the workspace had been sized
+  }
   return DYB_OK;
 }
 
@@ -1032,6 +1081,37 @@ struct ParTailGuard {
     if (sC != st && hipEventRecord(eC, sC) == hipSuccess) (void)hipStreamWaitEvent(st, eC, 0);
   }
 };
+// Exemplar bank: every replica of the current scope picks (nearest centre of its pooled feature in pass P, member draw bank_draw[r]) on
+// `sel` - the stream P's forward was issued on - and the chosen exemplars are gathered into the replicas' exemplar staging on `gat`, the
+// stream the exemplar pass runs on, behind the event `ev` when the two differ.  The staging's previous readers (the last level's
+// exemplar forward / backward) are ordered before the gather: on `gat` itself, or - they ran on another stream - by that level's join
+// (par_ev[5]) and this level's fork (par_ev[0]).  C.in[IN_EX_*] become the staging areas; the draw indices advance.
+static int bank_retrieve(Stepper& S, LevelCtx& C, Pass& P, hipStream_t sel, hipStream_t gat, hipEvent_t ev) {
+  const DybRep& R = dyb_rep_current();
+  int rows[DYB_MAX_REPLICAS];
+  for (int i = 0; i < R.n; ++i) rows[i] = S.nrep == 1 ? 0 : dyb_rep_phys(R, i);
+  const int K = S.bank_clusters, cap = S.bank_pick_capacity;
+  const int chunk = std::max(16, dyb_cdiv(K, BANK_MAX_CHUNKS));
+  RUN(dyb_retrieve_select(P.acts + S.fca.off[5], S.blob, rows, R.n, S.bank_centers, S.bank_inv_norm, K, S.bank_member_ptr, S.bank_member_idx,
+                          S.bank_members, S.bank_items, S.bank_draw, S.bank_seed, 0, S.bank_picks, (size_t)cap * 2 * sizeof(int), cap, chunk, 0,
+                          S.retr_ws, dyb_retrieve_workspace_bytes(S.nrep, BANK_MAX_CHUNKS, 1), sel));
+  if (gat != sel) {
+    HIPOK(hipEventRecord(ev, sel));
+    HIPOK(hipStreamWaitEvent(gat, ev, 0));
+  }
+  float* dst[5];
+  size_t stride[5];
+  for (int k = 0; k < 5; ++k) {
+    DYB_REQUIRE(S.in_stage[IN_EX_IMG + k], DYB_ERR_ARG);
+    dst[k] = S.in_stage[IN_EX_IMG + k];
+    stride[k] = S.blob;
+  }
+  RUN(dyb_exemplar_gather(S.bank_picks, (size_t)cap * 2 * sizeof(int), cap, rows, R.n, S.bank_draw, S.bank_img, S.bank_kp, S.bank_pose,
+                          S.bank_betas, S.bank_pose3d, S.bank_items, dst, stride, gat));
+  for (int k = 0; k < 5; ++k) C.in[IN_EX_IMG + k] = S.in_stage[IN_EX_IMG + k];
+  for (int i = 0; i < R.n; ++i) ++S.bank_draw[rows[i]];
+  return DYB_OK;
+}
 // the weight gradients' fused update epilogues ("fuse_fast", "fuse_adam") exist for single-pass levels: never with the full term set
 static bool fused_epilogues(const Stepper& S) { return !S.full; }
 // One level (reference base_adaptor.py:222-317 lower / upper_level_adaptation) at weights `cur` through pass P: forward, frame head,
@@ -1066,7 +1146,7 @@ static int level(Stepper& S, LevelCtx& C, Pass& P, const float* cur, float* nxt,
   if (par) {
     for (int i = 0; i < 2; ++i)
       if (!S.par_stream[i]) HIPOK(hipStreamCreateWithFlags(&S.par_stream[i], hipStreamNonBlocking));
-    for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < 9; ++i)
       if (!S.par_ev[i]) HIPOK(hipEventCreateWithFlags(&S.par_ev[i], hipEventDisableTiming));
     sB = S.par_stream[0]; sC = S.par_stream[1];
     HIPOK(hipEventRecord(S.par_ev[0], st));
@@ -1123,6 +1203,8 @@ static int level(Stepper& S, LevelCtx& C, Pass& P, const float* cur, float* nxt,
                                  S.exg_joints, nullptr, nullptr, 0, s);
   };
   if (par && label) {
+    // exemplar bank: select on the chain right behind the level's forward, gather + labelled pass on the exemplar stream behind it
+    if (bank_bound(S)) RUN(bank_retrieve(S, C, P, st, sC, S.par_ev[8]));
     DYB_REQUIRE(C.in[IN_EX_IMG] && C.in[IN_EX_KP] && C.in[IN_EX_POSE] && C.in[IN_EX_BETAS] && C.in[IN_EX_POSE3D], DYB_ERR_ARG);
     RUN(label_pass_forward_and_term(sC, false));
     HIPOK(hipEventRecord(S.par_ev[4], sC));
@@ -1167,8 +1249,11 @@ static int level(Stepper& S, LevelCtx& C, Pass& P, const float* cur, float* nxt,
     }
   }
   if (label && !par) {
-    // retrieval (base_adaptor.py:82-96) happens on the host: hand it the pooled feature of this level's forward
-    if (S.nrep > 1 && S.retrieve_rep) {
+    // retrieval (base_adaptor.py:82-96): the exemplar bank's two kernels in line, or on the host - hand it the pooled feature of this
+    // level's forward
+    if (bank_bound(S)) {
+      RUN(bank_retrieve(S, C, P, st, st, nullptr));
+    } else if (S.nrep > 1 && S.retrieve_rep) {
       DYB_REQUIRE(S.feat5_out, DYB_ERR_ARG);
       const DybRep& R = dyb_rep_current();
       RUN(dyb_scale_add(nullptr, P.acts + S.fca.off[5], nullptr, S.feat5_out, (size_t)B * 2048, st));     // every replica's feature, one launch
@@ -1479,6 +1564,15 @@ static int adapt(Stepper& S, const void* const* inputs, int nk, int record_slot,
                  hipStream_t aux, hipStream_t side) {
   RUN(check_ready(S));
   DYB_REQUIRE((nk == IN_COUNT) == (S.full != 0) && (!S.full || S.B <= 16), DYB_ERR_UNSUPPORTED);
+  // a frame step that fails must leave the bank's draw indices where they were: a retry draws the same members (ADVICE: stale state
+  // survives an error return)
+  struct DrawGuard {
+    Stepper& S;
+    unsigned long long saved[DYB_MAX_REPLICAS];
+    bool ok = false;
+    explicit DrawGuard(Stepper& s) : S(s) { memcpy(saved, S.bank_draw, sizeof saved); }
+    ~DrawGuard() { if (!ok) memcpy(S.bank_draw, saved, sizeof saved); }
+  } draws(S);
   const int n = S.nrep;
   int extra[DYB_MAX_REPLICAS] = {};
   LevelCtx C{};
@@ -1518,6 +1612,7 @@ static int adapt(Stepper& S, const void* const* inputs, int nk, int record_slot,
   }
   if (extra_steps)
     for (int r = 0; r < n; ++r) extra_steps[r] = extra[r];
+  draws.ok = rc == DYB_OK;
   return rc;
 }
 // One sequence, frame-loss set: image [B][3][H][W], kp2d [B][49][3]; gt_pose / gt_betas / gender may be NULL with metrics = 0.

@@ -2,7 +2,7 @@
 // dyb_stepper_get_i / _f, environment variable or NULL, type I int | F double | P pointer, locked once the workspace is bound, meaning).
 // The name lookup of the setters and getters and the environment reads in dyb_stepper_create (int rows; a later set_i wins) are
 // generated from this list; defaults and the longer notes sit with the members in struct Stepper.  Keys with code of their own:
-// "adam_step", "adam_step_<replica>", "drop_seed", "drop_offset", "replicas" (locked), "logs_bytes", "result_floats" (get_i: B * 20900), the "smpl_*" / "smpli_*" table
+// "adam_step", "adam_step_<replica>", "bank_seed", "bank_draw_<replica>", "drop_seed", "drop_offset", "replicas" (locked), "logs_bytes", "result_floats" (get_i: B * 20900), the "smpl_*" / "smpli_*" table
 // families and the range check of "drop_p" (0 <= p < 1).  Measurements: DESIGN.md section 5.
 #pragma once
 #define DYB_STEPPER_OPTIONS_I(X)                                                                                                              \
@@ -34,7 +34,12 @@
   X(kp_set, "kp_set", nullptr, I, 0, "keypoint window of the 2D term and the motion term: 0 gt24 (joints 25..48) | 1 op25 (joints 0..24)")   \
   X(record_capacity, "record_capacity", nullptr, I, 0, "metric-record slots behind `records`")                                                \
   X(loss_capacity, "loss_capacity", nullptr, I, 0, "frames behind `loss_log` / `gate_log`")                                                   \
-  X(result_capacity, "result_capacity", nullptr, I, 0, "rows behind `results` (a frame's final inferences go to row loss_slot mod this)")
+  X(result_capacity, "result_capacity", nullptr, I, 0, "rows behind `results` (a frame's final inferences go to row loss_slot mod this)")      \
+  X(bank_items, "bank_items", nullptr, I, 0, "exemplar bank: items in the five tables")                                                       \
+  X(bank_clusters, "bank_clusters", nullptr, I, 0, "exemplar bank: cluster centres")                                                          \
+  X(bank_members, "bank_members", nullptr, I, 0, "exemplar bank: entries of bank_member_idx")                                                 \
+  X(bank_pick_capacity, "bank_pick_capacity", nullptr, I, 0, "exemplar bank: rows of each replica's pick log (row = draw index mod this)")    \
+  X(bank_on_device, "bank_on_device", "DYB_BANK_ON_DEVICE", I, 0, "exemplar bank: 1 select / gather kernels inside the level | 0 ignore the bank (callback route; A/B)")
 #define DYB_STEPPER_OPTIONS_F(X)                                                                                                              \
   X(lr, "lr", nullptr, F, 0, "Adam learning rate")                                                                                            \
   X(beta1, "beta1", nullptr, F, 0, "Adam beta1")                                                                                              \
@@ -70,4 +75,14 @@
   X(results, "results", nullptr, P, 0, "[replicas][result_capacity][result_floats] result ring: each replica's last final inference of a frame") \
   X(retrieve, "retrieve_fn", nullptr, P, 0, "int (*)(user, level, out[5]): exemplars of one sequence")                                        \
   X(retrieve_rep, "retrieve_rep_fn", nullptr, P, 0, "int (*)(user, level, physical replica, out[5]): exemplars of a replica")                 \
-  X(retrieve_user, "retrieve_user", nullptr, P, 0, "first argument of the callbacks")
+  X(retrieve_user, "retrieve_user", nullptr, P, 0, "first argument of the callbacks")                                                         \
+  X(bank_img, "bank_img", nullptr, P, 0, "exemplar bank: [items][3][224][224] crops")                                                         \
+  X(bank_kp, "bank_keypoints", nullptr, P, 0, "exemplar bank: [items][49][3]")                                                                \
+  X(bank_pose, "bank_pose", nullptr, P, 0, "exemplar bank: [items][72]")                                                                      \
+  X(bank_betas, "bank_betas", nullptr, P, 0, "exemplar bank: [items][10]")                                                                    \
+  X(bank_pose3d, "bank_pose_3d", nullptr, P, 0, "exemplar bank: [items][24][4]")                                                              \
+  X(bank_centers, "bank_centers", nullptr, P, 0, "exemplar bank: [clusters][2048] centres")                                                   \
+  X(bank_inv_norm, "bank_center_inv_norm", nullptr, P, 0, "exemplar bank: [clusters] 1 / |centre|")                                           \
+  X(bank_member_ptr, "bank_member_ptr", nullptr, P, 0, "exemplar bank: [clusters + 1] int, CSR offsets of the clusters' members")             \
+  X(bank_member_idx, "bank_member_idx", nullptr, P, 0, "exemplar bank: [members] int, item indices")                                          \
+  X(bank_picks, "bank_picks", nullptr, P, 0, "[replicas][bank_pick_capacity][2] int: (cluster, item) of every draw")

@@ -215,7 +215,28 @@ class NativeStepper:
             self.feat5 = self.logs[:, o_feat:o_feat + n_feat].view(S, B, 2048)
             sp("gate_host", self.gate_host); sp("gate_log", self.gate_log); sp("feat5_out", self.feat5)
             self._cb = None
-            if (o.lower_level_mixtrain or o.upper_level_mixtrain) and getattr(adaptor, "bundle", None) is None:
+            self.bank, self.bank_picks, self._bank_dev = None, None, False
+            feature_driven = (o.lower_level_mixtrain or o.upper_level_mixtrain) and getattr(adaptor, "bundle", None) is None
+            if feature_driven and getattr(adaptor, "exemplar_bank", None) is not None:
+                # --exemplar_bank 1: the resident retrieval set.  Bound to the stepper, its levels select and gather on the device and no
+                # callback is installed; "bank_on_device" 0 (A/B measurement, tests) keeps the callback route below, whose
+                # a.retrieval() follows the bank's draw rule too - both routes log their picks in bank_picks
+                bank = self.bank = adaptor.exemplar_bank
+                if any(getattr(a, "exemplar_bank", None) is not bank for a in ads):
+                    raise ValueError("exemplar bank: the sequences of a group share one bank")
+                self.bank_pick_capacity = BANK_PICK_ROWS
+                self.bank_picks = torch.full((S, BANK_PICK_ROWS, 2), -1, dtype=torch.int32, device=dev)
+                on = getattr(o, "bank_on_device", None)
+                self._bank_dev = bool(int(os.environ.get("DYB_BANK_ON_DEVICE", "1")) if on is None else on)
+                si("bank_on_device", int(self._bank_dev))
+                if self._bank_dev:
+                    for k, t in (("bank_img", bank.img), ("bank_keypoints", bank.keypoints), ("bank_pose", bank.pose), ("bank_betas", bank.betas),
+                                 ("bank_pose_3d", bank.pose_3d), ("bank_centers", bank.centers), ("bank_center_inv_norm", bank.center_inv_norm),
+                                 ("bank_member_ptr", bank.member_ptr), ("bank_member_idx", bank.member_idx), ("bank_picks", self.bank_picks)):
+                        sp(k, t)
+                    si("bank_items", bank.items); si("bank_clusters", bank.clusters); si("bank_members", bank.members)
+                    si("bank_pick_capacity", BANK_PICK_ROWS); si("bank_seed", int(o.seed))
+            if feature_driven and not self._bank_dev:
                 # retrieval (base_adaptor.py:82-96) stays on the host: argmin over the cluster table + a seeded sample, per sequence
                 self._ex_keep = [None] * S
 
@@ -225,6 +246,8 @@ class NativeStepper:
                     a = ads[r]
                     ex = a.retrieval(self.feat5[r])
                     a._last_h36m = ex
+                    if self.bank is not None:                # the callback route's pick log: what the device route's kernels write
+                        self.bank_picks[r, (a._bank_draw - 1) % self.bank_pick_capacity] = torch.tensor(a._bank_last_pick, dtype=torch.int32)
                     keep = [ex["img"].contiguous().float(), ex["keypoints"].contiguous().float(), ex["pose"].contiguous().float(),
                             ex["betas"].contiguous().float(), ex["pose_3d"].contiguous().float()]
                     self._ex_keep[r] = keep
@@ -315,11 +338,14 @@ class NativeStepper:
         if full:
             self._cb_error = None
             self._drop_begin()
+            self._bank_begin(rows)
             rc = self.lib.dyb_stepper_adapt_frames_full(self.h, ctypes.cast(ptrs, ctypes.c_void_p), slot0, f, ctypes.cast(extra, ctypes.c_void_p),
                                                         st, aux)
             if getattr(self, "_cb_error", None) is not None:
                 raise self._cb_error
             self._drop_end()
+            if rc == 0:
+                self._bank_end(rows)
         else:
             rc = self.lib.dyb_stepper_adapt_frames(self.h, ctypes.cast(ptrs, ctypes.c_void_p), slot0, f, st, aux, side)
         check(rc, "dyb_stepper_adapt_frames_full" if full else "dyb_stepper_adapt_frames")
@@ -374,6 +400,31 @@ class NativeStepper:
             seed = int(torch.initial_seed()) & ((1 << 64) - 1)
             check(self.lib.dyb_stepper_set_i(self.h, b"drop_seed", seed - (1 << 64) if seed >= (1 << 63) else seed), "set_i drop_seed")
             check(self.lib.dyb_stepper_set_i(self.h, b"drop_offset", _H._DROP_CALLS[0] + 1), "set_i drop_offset")
+
+    def _bank_begin(self, rows):
+        """exemplar bank on the device: hand the stepper every active sequence's draw index (the adaptors own the counters, as they own
+        the Adam step counts)"""
+        if getattr(self, "_bank_dev", False):
+            for r in rows:
+                check(self.lib.dyb_stepper_set_i(self.h, f"bank_draw_{r}".encode(), int(self.adaptors[r]._bank_draw)), "set_i bank_draw")
+
+    def _bank_end(self, rows):
+        """... and take them back after the frame; the adaptor's `_last_h36m` is built from the sequence's latest pick when it is read"""
+        if getattr(self, "_bank_dev", False):
+            for r in rows:
+                a = self.adaptors[r]
+                d = int(self.lib.dyb_stepper_get_i(self.h, f"bank_draw_{r}".encode()))
+                if d != a._bank_draw:
+                    a._bank_draw = d
+                    a.defer_last_h36m(lambda bank=self.bank, row=self.bank_picks[r, (d - 1) % self.bank_pick_capacity]: bank.batch_of_pick(row))
+
+    def picks(self, replica: int = 0) -> torch.Tensor:
+        """[bank_pick_capacity][2] int32 view of `replica`'s pick log: row (draw index mod capacity) = (cluster, item); -1 = not
+        drawn yet (item -1 with a cluster: that cluster was empty)."""
+        log = getattr(self, "bank_picks", None)
+        if log is None:
+            raise RuntimeError("native stepper: no exemplar bank")
+        return log[replica]
 
     def _drop_end(self):
         if getattr(self, "teacher_train", False):
@@ -454,6 +505,7 @@ class NativeStepper:
 
 
 RESULT_RING_ROWS = 2
+BANK_PICK_ROWS = 256           # rows of a sequence's pick log (a ring: a frame draws at most inner_step + 1 + optim_steps times)
 
 
 # Sequences per launch from which the throughput schedule (dy materialised once per layer by the one-pass GroupNorm backward, plain

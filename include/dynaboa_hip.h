@@ -575,12 +575,20 @@ int dyb_render_scenes(const dyb_render_scene* scenes, int nscenes, const float* 
  * sharing one GPU).  Keys: csrc/dyb_stepper_options.h lists every option once - key, type (set_i / set_f / set_p), environment
  * variable, whether it is locked once the workspace is bound ("replicas", "fuse_fast", "full": DYB_ERR_ARG afterwards), meaning;
  * get_i / get_f return any int / double option by its key.  With code of their own:
- *   set_i: adam_step, adam_step_<replica>, replicas (1..64), logs_bytes, drop_seed, drop_offset
+ *   set_i: adam_step, adam_step_<replica>, replicas (1..64), logs_bytes, drop_seed, drop_offset, bank_seed, bank_draw_<replica>
  *   set_p: smpl_{neutral,male,female}_{0..6} and smpli_{...}_{0..2} (the table order of dyb_lbs_fwd)
- *   get_i: adam_step, adam_step_<replica>, drop_used, slots_per_frame, result_floats (floats per row of the result ring), record_floats (floats per metric record: pred14 [B][14][3] |
+ *   get_i: adam_step, adam_step_<replica>, bank_seed, bank_draw_<replica>, drop_used, slots_per_frame, result_floats (floats per row of the result ring), record_floats (floats per metric record: pred14 [B][14][3] |
  *          gt14 [B][14][3] | mpjpe [B] | pve), loss_floats (floats per frame in loss_log: (inner_step + 1) x {s2d, shape prior, pose
  *          prior, weighted total}; full term set: 16 per level, + optim_steps levels with the dynamic loop)
  * Unknown keys are errors.
+ * Exemplar bank (full term set, batch 1): with the ten "bank_*" pointers and bank_items / bank_clusters / bank_members /
+ * bank_pick_capacity set (and "bank_on_device" 1, the default), a level with a labelled term runs dyb_retrieve_select on the
+ * chain's stream behind its forward - every replica of the launch from its own pooled feature, draw index bank_draw_<replica>,
+ * seed bank_seed - and dyb_exemplar_gather into the replicas' exemplar inputs on the stream of the exemplar pass, behind an
+ * event: no host callback, the parallel passes stay on, the exemplar entries of `inputs` stay NULL.  bank_draw_<replica> advances
+ * by one per labelled level of that replica (not at all when the frame step returns an error); row (draw mod bank_pick_capacity)
+ * of bank_picks[replica] receives (cluster, item), item -1 if the nearest cluster was empty (the replica's exemplar inputs are
+ * then not rewritten).  A bank together with retrieve_fn / retrieve_rep_fn is DYB_ERR_ARG.
  * dyb_stepper_adapt_frame: gender is int64 [B]; gt_* / gender may be NULL with metrics = 0.  Records go to slots
  * record_slot.. (one per inner step when eval_lower, then the final one).  `aux`: weight-gradient stream (may be NULL);
  * `side`: stream for the final no-grad forward + its metrics (may be NULL), overlapped with the next frame.
@@ -655,6 +663,30 @@ const float* dyb_stepper_output(const void* stepper, int which);
  * (s, tx, ty) | 1 pad float that is never written (20900 floats, a multiple of 16 bytes).  rotmat [B][24][9], state [B][160] (shape
  * at 144, cam at 154), verts [B][6890][3] (8-byte aligned), out [B][20900] (16-byte aligned). */
 int dyb_result_pack(const float* rotmat, const float* state, const float* verts, float* out, int B, dyb_stream_t stream);
+
+/* Device-resident exemplar bank (csrc/retrieval.hip; reference base_adaptor.py:82-96 without the host): dyb_retrieve_select picks,
+ * for each of nrows feature rows of 2048 floats, the centre with the largest cos_k = dot(x, c_k) * center_inv_norm[k] (ties: the
+ * LOWEST index; independent of `chunk`, the centres per workgroup, <= 0 = 16) and draws a member of that cluster:
+ * w = first word of philox4x32_10(counter = (draw lo, draw hi, sample, 0), key = (seed lo, seed hi)),
+ * item = member_idx[member_ptr[c] + mulhi32(w, member_ptr[c + 1] - member_ptr[c])].  Row i belongs to "physical replica" rows[i]
+ * (HOST array, 0 .. 63, nrows <= 64): its feature is at feat + rows[i] * feat_stride BYTES (16-byte aligned), its draw index
+ * draws[rows[i]] (HOST array indexed by replica), its pick log at picks + rows[i] * picks_stride bytes - [pick_capacity][2] int32,
+ * row (draw mod pick_capacity) receives (cluster, item).  No allocation; stream ordered; check == 0 never synchronises and an empty
+ * nearest cluster (or tables pointing outside the bank) leaves item -1 in the log; check != 0 waits for the stream and returns
+ * DYB_ERR_ARG for such a row.  K <= 0, n_items <= 0, more than 64 rows: DYB_ERR_ARG.
+ * dyb_exemplar_gather copies, for each row, bank item picks[r][draws[r] mod pick_capacity][1] into the replica's five exemplar
+ * inputs: dst5 / dst_stride5 are HOST arrays of replica 0's destinations (img [3][224][224], keypoints [49][3], pose [72], betas
+ * [10], pose_3d [24][4]; img 16-byte aligned) and the bytes between consecutive replicas.  Rows whose logged item is outside
+ * [0, n_items) are left untouched. */
+size_t dyb_retrieve_workspace_bytes(int rows, int K, int chunk);
+int dyb_retrieve_select(const float* feat, size_t feat_stride, const int* rows, int nrows, const float* centers,
+                        const float* center_inv_norm, int K, const int* member_ptr, const int* member_idx, int n_members,
+                        int n_items, const unsigned long long* draws, unsigned long long seed, int sample, int* picks,
+                        size_t picks_stride, int pick_capacity, int chunk, int check, void* ws, size_t ws_bytes,
+                        dyb_stream_t stream);
+int dyb_exemplar_gather(const int* picks, size_t picks_stride, int pick_capacity, const int* rows, int nrows,
+                        const unsigned long long* draws, const float* img, const float* kp, const float* pose, const float* betas,
+                        const float* pose3d, int n_items, float* const* dst5, const size_t* dst_stride5, dyb_stream_t stream);
 
 /* HMR in train() mode: nn.Dropout(p) after fc1 / fc2 of every regressor iteration (reference model/hmr.py:84,86,165,169 -
  * the reference's mean teacher runs like this, base_adaptor.py:151-158 never calls teacher.eval()).  Masks are
