@@ -688,6 +688,28 @@ int dyb_exemplar_gather(const int* picks, size_t picks_stride, int pick_capacity
                         const unsigned long long* draws, const float* img, const float* kp, const float* pose, const float* betas,
                         const float* pose3d, int n_items, float* const* dst5, const size_t* dst_stride5, dyb_stream_t stream);
 
+/* Spherical k-means for building the retrieval index (csrc/kmeans.hip; dynaboa_amd/retrieval_index.py drives the Lloyd loop).
+ * x: N rows of D floats, row i at x + i * x_stride_bytes (16-byte aligned base and pitch, pitch >= 4 D); centers [K][D] contiguous,
+ * un-normalised.  Shapes: N >= 1, D a multiple of 32, 1 <= K <= 1024 - otherwise DYB_ERR_UNSUPPORTED (D, K) or DYB_ERR_ARG, before
+ * any launch and with every output untouched; a workspace smaller than the matching *_workspace_bytes is DYB_ERR_WORKSPACE.  No
+ * allocation, stream ordered, no synchronisation.
+ * dyb_rows_inv_norm: inv_norm[i] = 1 / max(|x_i|, 1e-8), the clamp of torch.cosine_similarity.
+ * dyb_kmeans_assign: assign[i] = the centre of highest cosine (dot(x_i, c_k) * x_inv_norm[i]) * center_inv_norm[k], ties to the
+ * LOWEST index (the rule of dyb_retrieve_select); best[i] = that cosine; changed[0] = rows whose assign differs from the value
+ * passed in (assign is read and rewritten: fill it with -1 before the first call); counts[k] = members of k; ws = one fp64 partial
+ * sum of best per 128 rows (ceil(N / 128) doubles, rows in order): the host adds them in index order for the objective.
+ * dyb_kmeans_update: centers[k] = (sum over members of x_i * x_inv_norm[i]) / counts[k]; counts[k] <= 0 leaves row k as it is.  No
+ * floating-point atomics: the summation order depends on (N, D, K) only, two calls return equal bytes.  counts must match assign
+ * (the host may have corrected both for empty clusters); entries of assign outside 0 .. K - 1 belong to no cluster. */
+int dyb_rows_inv_norm(const float* x, size_t x_stride_bytes, int N, int D, float* inv_norm, dyb_stream_t stream);
+size_t dyb_kmeans_assign_workspace_bytes(int N, int D, int K);
+int dyb_kmeans_assign(const float* x, size_t x_stride_bytes, const float* x_inv_norm, int N, int D, const float* centers,
+                      const float* center_inv_norm, int K, int* assign, float* best, int* changed, int* counts, void* ws,
+                      size_t ws_bytes, dyb_stream_t stream);
+size_t dyb_kmeans_update_workspace_bytes(int N, int D, int K);
+int dyb_kmeans_update(const float* x, size_t x_stride_bytes, const float* x_inv_norm, int N, int D, const int* assign,
+                      const int* counts, int K, float* centers, void* ws, size_t ws_bytes, dyb_stream_t stream);
+
 /* HMR in train() mode: nn.Dropout(p) after fc1 / fc2 of every regressor iteration (reference model/hmr.py:84,86,165,169 -
  * the reference's mean teacher runs like this, base_adaptor.py:151-158 never calls teacher.eval()).  Masks are
  * counter-based (Philox-4x32-10) functions of (seed, offset, iteration, element): a backward regenerates them from the same
