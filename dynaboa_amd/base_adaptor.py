@@ -487,7 +487,8 @@ class BaseAdaptor:
         key = (int(width), int(height))
         if key not in cache:
             cache.clear()                                            # frames of one stream share a size: keep one
-            cache[key] = Renderer(resolution=key, orig_img=True, wireframe=False, faces=self.smpl_neutral.faces, device=self.device)
+            cache[key] = Renderer(resolution=key, orig_img=True, wire=bool(getattr(self.options, "wireframe", 0)),
+                                  faces=self.smpl_neutral.faces, device=self.device)
         return cache[key]
 
     def ragged_renderer(self):
@@ -495,8 +496,8 @@ class BaseAdaptor:
         r = self.__dict__.get("_ragged_renderer")
         if r is None:
             from .render import Renderer
-            r = self._ragged_renderer = Renderer(resolution=(224, 224), orig_img=True, wireframe=False, faces=self.smpl_neutral.faces,
-                                                 device=self.device)
+            r = self._ragged_renderer = Renderer(resolution=(224, 224), orig_img=True, wire=bool(getattr(self.options, "wireframe", 0)),
+                                                 faces=self.smpl_neutral.faces, device=self.device)
         return r
 
     def result_step(self):
@@ -508,7 +509,34 @@ class BaseAdaptor:
     def overlay_jobs(self, vts, cam, images, name, bbox, prefix=None):
         """The overlays save_results writes for this batch, not drawn yet: [(frame uint8 (H, W, 3) on the device, vertices
         (6890, 3), camera (4,) = (sx, sy, tx, ty), path)] - over the original frame files when they exist, else over the
-        de-normalised crops.  A group collects the jobs of all its sequences and draws them in one ragged launch (draw_overlays)."""
+        de-normalised crops.  A group collects the jobs of all its sequences and draws them in one ragged launch (draw_overlays).
+        --side_view DEG: every overlay job is followed by a second one, (white canvas of the frame's size, vertices, the same camera,
+        None, model matrix of the turn by DEG about Y) - the right half of the picture written at the first job's path.
+        --save_obj 1: ``exppath/mesh/{prefix}_{n}.obj`` is written here, the mesh turned by Rx as the reference exports it (one file
+        per frame beside the picture; the reference's single ``demo.obj`` in the working directory, overwritten by every frame,
+        is not reproduced)."""
+        jobs = self._overlay_jobs(vts, cam, images, name, bbox, prefix)
+        if getattr(self.options, "save_obj", 0):
+            from .render import turned_vertices, write_obj
+            meshdir = os.path.join(self.exppath, "mesh")
+            os.makedirs(meshdir, exist_ok=True)
+            for j in jobs:
+                stem = os.path.splitext(os.path.basename(j[3]))[0]
+                write_obj(os.path.join(meshdir, stem + ".obj"), turned_vertices(j[1]), self.ragged_renderer().faces)
+        deg = float(getattr(self.options, "side_view", 0) or 0)
+        if not deg:
+            return jobs
+        from .render import side_view_matrix
+        model = side_view_matrix(deg, [0, 1, 0])
+        white, both = {}, []
+        for frame, v, c, path in jobs:
+            key = tuple(frame.shape)
+            if key not in white:                                     # frames of one size share one canvas: it is only read
+                white[key] = torch.full_like(frame, 255)
+            both += [(frame, v, c, path), (white[key], v, c, None, model)]
+        return both
+
+    def _overlay_jobs(self, vts, cam, images, name, bbox, prefix):
         from .render import convert_crop_cam_to_orig_img
         vts, cam = vts.detach(), cam.detach().float()
         outdir = os.path.join(self.exppath, "image")
@@ -549,13 +577,27 @@ class BaseAdaptor:
 
 def draw_overlays(renderer, jobs, color):
     """Draw overlay jobs (BaseAdaptor.overlay_jobs, of one adaptor or of all sequences of a group's step) - one ragged launch per 64
-    meshes, each over its own frame at its own size - and write the PNGs.  -> the written paths."""
+    meshes, each over its own frame at its own size - and write the PNGs.  A job without a path (a side view) is the right half of
+    the job before it: the two are drawn by the same launch (a launch then draws at most 32 people: 64 descriptors) and joined on
+    the device before the one copy to the host.  -> the written paths."""
     from PIL import Image
     paths = []
-    for lo in range(0, len(jobs), 64):
-        part = jobs[lo:lo + 64]
-        pics = renderer.render_many([j[0] for j in part], [j[1] for j in part], torch.stack([j[2] for j in part]), color=color)
-        for pic, j in zip(pics, part):
+    lo = 0
+    while lo < len(jobs):
+        hi = min(lo + 64, len(jobs))
+        if hi < len(jobs) and jobs[hi][3] is None:                   # a picture's two halves stay in one launch
+            hi -= 1
+        part = jobs[lo:hi]
+        models = [j[4] if len(j) > 4 else None for j in part]
+        pics = renderer.render_many([j[0] for j in part], [j[1] for j in part], torch.stack([j[2] for j in part]), color=color,
+                                    models=models if any(m is not None for m in models) else None)
+        for k, j in enumerate(part):
+            if j[3] is None:
+                continue
+            pic = pics[k]
+            if k + 1 < len(part) and part[k + 1][3] is None:
+                pic = torch.cat([pic, pics[k + 1]], 1)
             Image.fromarray(pic.cpu().numpy()).save(j[3])
             paths.append(j[3])
+        lo = hi
     return paths

@@ -35,6 +35,13 @@ parser.add_argument('--seq_seed', type=int, default=22)
 parser.add_argument('--model_file', type=str, default='data/basemodel.pt')
 parser.add_argument('--batch_size', type=int, default=1)
 parser.add_argument('--save_res', type=int, default=0, choices=[0, 1])
+parser.add_argument('--side_view', type=float, default=0.0,
+                    help='with --save_res 1: DEG != 0 makes every picture a panel of twice the width - the overlay on the left, the mesh '
+                         'turned by DEG degrees about Y over a white canvas on the right, under the same camera (270 is the usual choice)')
+parser.add_argument('--wireframe', type=int, default=0, choices=[0, 1],
+                    help='with --save_res 1: draw the overlay (and the side view) as a wireframe')
+parser.add_argument('--save_obj', type=int, default=0, choices=[0, 1],
+                    help='with --save_res 1: also write mesh/{prefix}_{n}.obj per frame, the mesh turned by 180 degrees about X')
 parser.add_argument('--lr', type=float, default=3e-6)
 parser.add_argument('--beta1', type=float, default=0.5)
 parser.add_argument('--beta2', type=float, default=0.9)

@@ -23,8 +23,24 @@
 //                    I = min(1, 0.3 + 0.35 sum_k max(0, n' . dir(L_k - p'))), L = (0,-1,1), (0,1,1), (1,1,2), no falloff;
 //                    pixel = round(255 I colour).  This is NOT pyrender's metallic-roughness shading (unpinned: pyrender is
 //                    absent from the build image); geometry, visibility and the light set-up are the reference's.
+//   model matrix     optional (dyb_render_opts.model, the _opt entries): one 3x3 fp32 matrix per mesh, row major, in this file's raw
+//                    model space; x' = (m0 x + m1 y) + m2 z and likewise y', z', one rounding per operation.  The reference turns
+//                    the mesh by Rx (180 degrees about X) and then by R(angle, axis); Rx is folded into the image coordinates here,
+//                    so the matrix handed down for a side view is Rx R Rx (render.py builds it in fp64 and rounds once).  A
+//                    pre-pass writes the turned vertices into the workspace and the kernels below read those rows: normals, face
+//                    set-up, depth and shading see the very numbers dyb_render_transform_verts gives, so a call with a matrix
+//                    equals, byte for byte, the call on vertices turned by that entry.  (-0 comes out as +0 under the identity.)
+//   wireframe        optional (dyb_render_opts.wireframe): a face gives a fragment at a pixel centre iff the centre is inside it by
+//                    the coverage rule above AND, for at least one of its edges e, w_e < 256 max(|dx_e|, |dy_e|) - w_e the
+//                    non-negative int64 edge function of e at the centre, dx_e / dy_e the snapped extents of e widened to int64:
+//                    the centre lies within one pixel of the edge along the edge's minor axis.  (256, not 128: an interior edge
+//                    gets a band from each of its two faces, a silhouette edge from its one front face only.)  Nearest fragment
+//                    wins, ties to the lower face index; depth and shading are the solid path's.  A pixel without a fragment keeps
+//                    the frame or falls through to the mesh beneath, even where a solid face would cover it: face_id -1, depth
+//                    +inf.  This follows OpenGL's line polygon mode as RenderFlags.ALL_WIREFRAME selects it - only line fragments
+//                    take part in the depth test - and is unpinned like the shading (pyrender is absent from the build image).
 //
-// Four kernels behind the three entries (uniform: N meshes at one frame size; ragged: every mesh over a frame of its own size;
+// Four kernels (and the matrix pre-pass) behind the three entries (uniform: N meshes at one frame size; ragged: every mesh over a frame of its own size;
 // scenes: several meshes over one frame): vertex normals (one thread per vertex), face set-up (one thread per face: snapped corners
 // + pixel box, an empty box for culled / off-image faces), the pixel box of a whole mesh (one workgroup per mesh; ragged and scene
 // entries), and one workgroup per 16x16 pixel tile that streams the face boxes 256 at a time, compacts the faces touching the tile
@@ -68,6 +84,11 @@ struct dyb_render_scene {
   int H, W;
   int mesh_begin, mesh_end;
 };
+// what the _opt forms of the entries take beside the plain arguments (include/dynaboa_hip.h declares the same struct); NULL = neither
+struct dyb_render_opts {
+  const float* model;                     // DEVICE [meshes][9], row major; NULL: identity
+  int wireframe;
+};
 // A call of any of the three entries as the kernels see it: scenes (a frame and the meshes [m0, m1) of the call's list over it, in
 // painter order) and meshes, as kernel arguments - no allocation, no copy, no host wait.  Sizes and mesh ranges are packed so that
 // 64 scenes and 64 meshes fit in the 4 KB a launch may carry (cameras and the scene entry's colours are device arrays for the same
@@ -90,6 +111,35 @@ struct RndTab {
 // padding (8), seven pointers (56), cr / cg / cb and V / F / use_box (24) = 3488 bytes of explicit arguments, and the 256 bytes of
 // implicit arguments the runtime appends.
 static_assert(sizeof(RndTab) + 8 + 56 + 24 + 256 <= 4096, "the table and the other arguments of the tile launch must fit in 4 KB");
+
+// ---- model matrix ----------------------------------------------------------------------------------------------------------------
+// o = M p, M row major: the one statement of that arithmetic (contraction is off: a product and a sum round separately)
+__device__ __forceinline__ void render_xform(const float* __restrict__ m, const float* __restrict__ p, float* __restrict__ o) {
+  const float x = p[0], y = p[1], z = p[2];
+  o[0] = (m[0] * x + m[1] * y) + m[2] * z;
+  o[1] = (m[3] * x + m[4] * y) + m[5] * z;
+  o[2] = (m[6] * x + m[7] * y) + m[8] * z;
+}
+// the pre-pass of a call with matrices: mesh n of the table -> row n of out [M][V][3]
+__global__ __launch_bounds__(256) void render_transform_tab_kernel(RndTab tab, const float* __restrict__ model, int V,
+                                                                   float* __restrict__ out) {
+  const int v = blockIdx.x * 256 + threadIdx.x, n = blockIdx.z;
+  if (v >= V) return;
+  render_xform(model + 9 * n, tab.verts[n] + 3 * (size_t)v, out + ((size_t)n * V + v) * 3);
+}
+// the exported form: verts [N][V][3] contiguous, flat over N V; model NULL: a copy
+__global__ __launch_bounds__(256) void render_transform_kernel(const float* __restrict__ verts, const float* __restrict__ model,
+                                                               float* __restrict__ out, long long total, int V) {
+  const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= total) return;
+  if (model) {
+    render_xform(model + 9 * (g / V), verts + 3 * g, out + 3 * g);
+  } else {
+    out[3 * g] = verts[3 * g];
+    out[3 * g + 1] = verts[3 * g + 1];
+    out[3 * g + 2] = verts[3 * g + 2];
+  }
+}
 
 // ---- vertex normals ------------------------------------------------------------------------------------------------------------
 // vertex v of the mesh at P -> its normal at o
@@ -230,6 +280,18 @@ __device__ __forceinline__ bool render_cover(int x0, int y0, int x1, int y1, int
   return (ea | eb | ec) >= 0;
 }
 
+// the wire rule for a covered centre: within one pixel of one of the face's edges, along that edge's minor axis
+__device__ __forceinline__ long long render_edge_reach(int ax, int ay, int bx, int by) {
+  long long dx = (long long)bx - ax, dy = (long long)by - ay;
+  dx = dx < 0 ? -dx : dx;
+  dy = dy < 0 ? -dy : dy;
+  return 256 * (dx > dy ? dx : dy);
+}
+__device__ __forceinline__ bool render_on_wire(int x0, int y0, int x1, int y1, int x2, int y2, const RenderHit& h) {
+  return h.wa < render_edge_reach(x2, y2, x1, y1) || h.wb < render_edge_reach(x1, y1, x0, y0) ||
+         h.wc < render_edge_reach(x0, y0, x2, y2);
+}
+
 // The frame under a tile -> the tile's LDS picture s_px, and back: 16-byte rows when the layout allows it (`wide`: W a multiple of 16
 // and 16-byte aligned bases), else one pixel per thread.  bg NULL: black.  The callers put a barrier between either of them and
 // any other use of s_px.
@@ -307,7 +369,8 @@ __device__ __forceinline__ void render_shade(const float* __restrict__ P, const 
 // whose box touches the tile are compacted into LDS with their corners and depths, and a pixel that takes part (`test`) keeps the
 // nearest face covering it in (best, best_f); ties go to the lower face index.  g: the running number of the chunk in this workgroup
 // - the LDS entries are double-buffered and the counters rotate by it (g = c for one mesh; a workgroup that walks several meshes
-// goes on counting).  Every thread of the workgroup calls it: it holds a barrier.
+// goes on counting).  Every thread of the workgroup calls it: it holds a barrier.  WIRE: only the fragments of the wire rule count.
+template <bool WIRE>
 __device__ __forceinline__ void render_chunk_nearest(const float* __restrict__ P, const int* __restrict__ faces, const int* __restrict__ C,
                                                      const int* __restrict__ B, int F, int c, int g, int tx0, int tx1, int ty0, int ty1,
                                                      int t, int i, int j, int px, int py, bool test, int (*s_xy)[6][RND_CHUNK],
@@ -342,6 +405,9 @@ __device__ __forceinline__ void render_chunk_nearest(const float* __restrict__ P
       if (!render_cover(s_xy[buf][0][e], s_xy[buf][1][e], s_xy[buf][2][e], s_xy[buf][3][e], s_xy[buf][4][e], s_xy[buf][5][e], px,
                         py, h))
         continue;
+      if (WIRE && !render_on_wire(s_xy[buf][0][e], s_xy[buf][1][e], s_xy[buf][2][e], s_xy[buf][3][e], s_xy[buf][4][e],
+                                  s_xy[buf][5][e], h))
+        continue;
       // weights of v0, v1, v2 = wa, wc, wb
       const float d = ((float)h.wa * s_z[buf][0][e] + (float)h.wc * s_z[buf][1][e] + (float)h.wb * s_z[buf][2][e]) / (float)h.area;
       const int f2 = s_f[buf][e];
@@ -363,7 +429,9 @@ __device__ __forceinline__ void render_chunk_nearest(const float* __restrict__ P
 // tests, and the walk ends when every live pixel of the tile is decided.  The pixel is shaded once, at the end, with the winner's
 // vertex rows, normals and colour: colors[3 m ..], or (cr, cg, cb) for every mesh when colors is NULL (the uniform and ragged
 // entries pass one colour as scalars and allocate nothing).  depth (uniform entry only: its scenes share one H x W, scene k's map
-// lies at depth + k H W): the winning face's depth, +inf where nothing is drawn.
+// lies at depth + k H W): the winning face's depth, +inf where nothing is drawn.  WIRE: the wireframe variant of the same body - a mesh
+// claims the pixels where it has a wire fragment only, so a tile a mesh covers without wires goes on to the mesh beneath.
+template <bool WIRE>
 __global__ __launch_bounds__(256) void render_tile_kernel(RndTab tab, int nscenes, const int* __restrict__ faces,
                                                           const float* __restrict__ vnorm, const int* __restrict__ fcoord,
                                                           const int* __restrict__ fbox, const int* __restrict__ mbox,
@@ -419,8 +487,8 @@ __global__ __launch_bounds__(256) void render_tile_kernel(RndTab tab, int nscene
     int best_f = -1;
     // a decided pixel tests nothing, but goes through the barriers with the others
     for (int c = 0; c < nchunks; ++c, ++g)
-      render_chunk_nearest(P, faces, C, B, F, c, g, tx0, tx1, ty0, ty1, t, i, j, px, py, live && win_m < 0, s_xy, s_box, s_z, s_f, s_cnt,
-                           best, best_f);
+      render_chunk_nearest<WIRE>(P, faces, C, B, F, c, g, tx0, tx1, ty0, ty1, t, i, j, px, py, live && win_m < 0, s_xy, s_box, s_z, s_f, s_cnt,
+                                 best, best_f);
     const bool won = live && win_m < 0 && best_f >= 0;
     if (won) {
       win_m = m;
@@ -463,13 +531,30 @@ extern "C" size_t dyb_render_var_workspace_bytes(int N, int V, int F) {
 }
 // scratch of the scene entry: that of the ragged entry for nmeshes meshes; none without a mesh
 extern "C" size_t dyb_render_scenes_workspace_bytes(int nmeshes, int V, int F) { return dyb_render_var_workspace_bytes(nmeshes, V, F); }
+// what a call with opts->model needs on top of its entry's own scratch, behind it: the turned vertices [N][V][3] fp32
+extern "C" size_t dyb_render_model_workspace_bytes(int N, int V) {
+  if (N <= 0 || V <= 0) return 0;
+  return rnd_align((size_t)N * V * 3 * sizeof(float));
+}
+
+// The matrices of a call, checked on the host before anything is launched: M x 9 floats come over on the call's stream, which is
+// waited for (calls without matrices never wait).  DYB_ERR_ARG for an entry that is not finite.
+static int render_check_model(const float* model, int M, hipStream_t st) {
+  float h[RND_MAX_N * 9];
+  if (hipMemcpyAsync(h, model, (size_t)M * 9 * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess) return DYB_ERR_LAUNCH;
+  if (hipStreamSynchronize(st) != hipSuccess) return DYB_ERR_LAUNCH;
+  for (int k = 0; k < 9 * M; ++k) DYB_REQUIRE(fabsf(h[k]) < __builtin_inff(), DYB_ERR_ARG);      // false for NaN as well
+  return DYB_OK;
+}
 
 // The launches of a checked call: the table's tile prefix is filled in, the workspace carved (the one statement of its layout: the
-// workspace_bytes functions above count these parts) and the kernels issued - normals, face set-up and, with use_box, the mesh boxes
-// for the M meshes of the list, then the tiles of the nscenes scenes.  use_box = 0: the workspace need not hold the mesh boxes.
+// workspace_bytes functions above count these parts) and the kernels issued - with matrices the pre-pass, after which the table
+// names the turned rows; normals, face set-up and, with use_box, the mesh boxes for the M meshes of the list, then the tiles of the
+// nscenes scenes.  use_box = 0: the workspace need not hold the mesh boxes.  base: the bytes of the entry's own scratch - the turned
+// rows lie behind them.
 static int render_launch(RndTab& tab, int nscenes, int M, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
                          const float* colors, float cr, float cg, float cb, float* depth, int V, int F, int use_box, void* ws,
-                         hipStream_t st) {
+                         size_t base, const dyb_render_opts* opts, hipStream_t st) {
   long long tiles = 0;
   for (int k = 0; k <= RND_MAX_N; ++k) {
     tab.tile0[k] = (int)tiles;
@@ -484,6 +569,12 @@ static int render_launch(RndTab& tab, int nscenes, int M, const int* faces, cons
   w += rnd_align((size_t)M * F * 2 * sizeof(int));
   int* mbox = use_box ? reinterpret_cast<int*>(w) : nullptr;
   if (M > 0) {
+    if (opts && opts->model) {
+      float* turned = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + base);
+      hipLaunchKernelGGL(render_transform_tab_kernel, dim3(dyb_cdiv(V, 256), 1, M), dim3(256), 0, st, tab, opts->model, V, turned);
+      DYB_CHECK_LAUNCH();
+      for (int m = 0; m < M; ++m) tab.verts[m] = turned + (size_t)m * V * 3;
+    }
     hipLaunchKernelGGL(render_vnormal_kernel, dim3(dyb_cdiv(V, 256), 1, M), dim3(256), 0, st, tab, faces, adj_ptr, adj_idx, V, F, vnorm);
     DYB_CHECK_LAUNCH();
     hipLaunchKernelGGL(render_face_setup_kernel, dim3(dyb_cdiv(F, 256), 1, M), dim3(256), 0, st, tab, faces, cam, V, F, fcoord, fbox);
@@ -493,22 +584,50 @@ static int render_launch(RndTab& tab, int nscenes, int M, const int* faces, cons
       DYB_CHECK_LAUNCH();
     }
   }
-  hipLaunchKernelGGL(render_tile_kernel, dim3((unsigned)tiles), dim3(256), 0, st, tab, nscenes, faces, (const float*)vnorm,
-                     (const int*)fcoord, (const int*)fbox, (const int*)mbox, colors, depth, cr, cg, cb, V, F, use_box);
+  if (opts && opts->wireframe)
+    hipLaunchKernelGGL(render_tile_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, st, tab, nscenes, faces, (const float*)vnorm,
+                       (const int*)fcoord, (const int*)fbox, (const int*)mbox, colors, depth, cr, cg, cb, V, F, use_box);
+  else
+    hipLaunchKernelGGL(render_tile_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, st, tab, nscenes, faces, (const float*)vnorm,
+                       (const int*)fcoord, (const int*)fbox, (const int*)mbox, colors, depth, cr, cg, cb, V, F, use_box);
+  DYB_CHECK_LAUNCH();
+  return DYB_OK;
+}
+// the last checks of an entry (they wait for the stream when there are matrices, so they come after every other check), then the launches
+static int render_checked_launch(RndTab& tab, int nscenes, int M, const int* faces, const int* adj_ptr, const int* adj_idx,
+                                 const float* cam, const float* colors, float cr, float cg, float cb, float* depth, int V, int F,
+                                 int use_box, void* ws, size_t ws_bytes, size_t base, const dyb_render_opts* opts, hipStream_t st) {
+  const bool turned = opts && opts->model && M > 0;
+  DYB_REQUIRE(ws_bytes >= base + (turned ? dyb_render_model_workspace_bytes(M, V) : 0), DYB_ERR_WORKSPACE);
+  if (turned) {
+    const int rc = render_check_model(opts->model, M, st);
+    if (rc != DYB_OK) return rc;
+  }
+  return render_launch(tab, nscenes, M, faces, adj_ptr, adj_idx, cam, colors, cr, cg, cb, depth, V, F, use_box, ws, base, opts, st);
+}
+
+// ---- the matrix arithmetic on its own ----------------------------------------------------------------------------------------------
+// out [N][V][3] = model[n] verts[n][v], the arithmetic the entries apply with opts->model; model NULL: out = verts, bit for bit.
+extern "C" int dyb_render_transform_verts(const float* verts, const float* model, float* out, int N, int V, hipStream_t st) {
+  DYB_REQUIRE(verts && out, DYB_ERR_ARG);
+  DYB_REQUIRE(N > 0 && V > 0, DYB_ERR_ARG);
+  DYB_REQUIRE(V <= (1 << 28) && (long long)N * V <= (1LL << 31), DYB_ERR_UNSUPPORTED);       // the flat grid stays inside 2^23 workgroups
+  const long long total = (long long)N * V;
+  hipLaunchKernelGGL(render_transform_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, verts, model, out, total, V);
   DYB_CHECK_LAUNCH();
   return DYB_OK;
 }
 
 // ---- the uniform entry: N meshes, one frame size, strided images -----------------------------------------------------------------
 // No pixel box: three launches, and the workspace has no room for the mesh boxes.
-extern "C" int dyb_render_meshes(const float* verts, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
-                                 const uint8_t* background, float col_r, float col_g, float col_b, uint8_t* out, int* face_id,
-                                 float* depth, int N, int V, int F, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int dyb_render_meshes_opt(const float* verts, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
+                                     const uint8_t* background, float col_r, float col_g, float col_b, uint8_t* out, int* face_id,
+                                     float* depth, int N, int V, int F, int H, int W, void* ws, size_t ws_bytes, hipStream_t st,
+                                     const dyb_render_opts* opts) {
   DYB_REQUIRE(verts && faces && adj_ptr && adj_idx && cam && out && ws, DYB_ERR_ARG);
   DYB_REQUIRE(N > 0 && V > 0 && F > 0 && H > 0 && W > 0, DYB_ERR_ARG);
   DYB_REQUIRE(N <= RND_MAX_N && H <= RND_MAX_DIM && W <= RND_MAX_DIM, DYB_ERR_UNSUPPORTED);
   DYB_REQUIRE(F <= (1 << 28) && V <= (1 << 28), DYB_ERR_UNSUPPORTED);                  // 3 F and 3 V stay inside int
-  DYB_REQUIRE(ws_bytes >= dyb_render_workspace_bytes(N, V, F), DYB_ERR_WORKSPACE);
   RndTab tab{};
   const size_t img = (size_t)H * W;
   for (int n = 0; n < N; ++n) {
@@ -517,15 +636,22 @@ extern "C" int dyb_render_meshes(const float* verts, const int* faces, const int
     tab.verts[n] = verts + (size_t)n * V * 3;
     tab.scene_of[n] = (unsigned char)n;
   }
-  return render_launch(tab, N, N, faces, adj_ptr, adj_idx, cam, nullptr, col_r, col_g, col_b, depth, V, F, 0, ws, st);
+  return render_checked_launch(tab, N, N, faces, adj_ptr, adj_idx, cam, nullptr, col_r, col_g, col_b, depth, V, F, 0, ws, ws_bytes,
+                               dyb_render_workspace_bytes(N, V, F), opts, st);
+}
+extern "C" int dyb_render_meshes(const float* verts, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
+                                 const uint8_t* background, float col_r, float col_g, float col_b, uint8_t* out, int* face_id,
+                                 float* depth, int N, int V, int F, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
+  return dyb_render_meshes_opt(verts, faces, adj_ptr, adj_idx, cam, background, col_r, col_g, col_b, out, face_id, depth, N, V, F, H, W, ws,
+                               ws_bytes, st, nullptr);
 }
 
 // ---- the ragged entry: every mesh with its own frame size and pointers ----------------------------------------------------------
 // desc: HOST table of N entries (copied into the launches' kernel arguments: free to reuse when the call returns).  flags bit 0:
 // leave the per-mesh pixel box out (every tile streams the face list, as the uniform entry does; same bytes - for measurements).
-extern "C" int dyb_render_meshes_var(const dyb_render_desc* desc, const int* faces, const int* adj_ptr, const int* adj_idx,
-                                     const float* cam, float col_r, float col_g, float col_b, int N, int V, int F, int flags, void* ws,
-                                     size_t ws_bytes, hipStream_t st) {
+extern "C" int dyb_render_meshes_var_opt(const dyb_render_desc* desc, const int* faces, const int* adj_ptr, const int* adj_idx,
+                                         const float* cam, float col_r, float col_g, float col_b, int N, int V, int F, int flags,
+                                         void* ws, size_t ws_bytes, hipStream_t st, const dyb_render_opts* opts) {
   DYB_REQUIRE(desc && faces && adj_ptr && adj_idx && cam && ws, DYB_ERR_ARG);
   DYB_REQUIRE(N > 0 && V > 0 && F > 0, DYB_ERR_ARG);
   DYB_REQUIRE(N <= RND_MAX_N, DYB_ERR_UNSUPPORTED);
@@ -540,8 +666,13 @@ extern "C" int dyb_render_meshes_var(const dyb_render_desc* desc, const int* fac
     tab.verts[n] = d.verts;
     tab.scene_of[n] = (unsigned char)n;
   }
-  DYB_REQUIRE(ws_bytes >= dyb_render_var_workspace_bytes(N, V, F), DYB_ERR_WORKSPACE);
-  return render_launch(tab, N, N, faces, adj_ptr, adj_idx, cam, nullptr, col_r, col_g, col_b, nullptr, V, F, (flags & 1) ? 0 : 1, ws, st);
+  return render_checked_launch(tab, N, N, faces, adj_ptr, adj_idx, cam, nullptr, col_r, col_g, col_b, nullptr, V, F, (flags & 1) ? 0 : 1, ws,
+                               ws_bytes, dyb_render_var_workspace_bytes(N, V, F), opts, st);
+}
+extern "C" int dyb_render_meshes_var(const dyb_render_desc* desc, const int* faces, const int* adj_ptr, const int* adj_idx,
+                                     const float* cam, float col_r, float col_g, float col_b, int N, int V, int F, int flags, void* ws,
+                                     size_t ws_bytes, hipStream_t st) {
+  return dyb_render_meshes_var_opt(desc, faces, adj_ptr, adj_idx, cam, col_r, col_g, col_b, N, V, F, flags, ws, ws_bytes, st, nullptr);
 }
 
 // ---- the scene entry: several meshes over ONE frame, in painter order ------------------------------------------------------------
@@ -549,9 +680,10 @@ extern "C" int dyb_render_meshes_var(const dyb_render_desc* desc, const int* fac
 // each mesh (it must agree with the scenes' ranges, which must tile 0 .. nmeshes in order).  Both are copied into the launches'
 // kernel arguments.  flags bit 0: leave the per-mesh pixel boxes out (same bytes - for measurements).  Without a mesh (ws may be
 // NULL) only the tiles are launched: they copy the frames.
-extern "C" int dyb_render_scenes(const dyb_render_scene* scenes, int nscenes, const float* const* mesh_verts, const int* mesh_scene,
-                                 const float* cam, const float* colors, const int* faces, const int* adj_ptr, const int* adj_idx,
-                                 int nmeshes, int V, int F, int flags, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int dyb_render_scenes_opt(const dyb_render_scene* scenes, int nscenes, const float* const* mesh_verts, const int* mesh_scene,
+                                     const float* cam, const float* colors, const int* faces, const int* adj_ptr, const int* adj_idx,
+                                     int nmeshes, int V, int F, int flags, void* ws, size_t ws_bytes, hipStream_t st,
+                                     const dyb_render_opts* opts) {
   DYB_REQUIRE(scenes && faces && adj_ptr && adj_idx, DYB_ERR_ARG);
   DYB_REQUIRE(nscenes > 0 && nmeshes >= 0 && V > 0 && F > 0, DYB_ERR_ARG);
   DYB_REQUIRE(nmeshes == 0 || (mesh_verts && mesh_scene && cam && colors && ws), DYB_ERR_ARG);
@@ -574,7 +706,13 @@ extern "C" int dyb_render_scenes(const dyb_render_scene* scenes, int nscenes, co
     }
   }
   DYB_REQUIRE(next == nmeshes, DYB_ERR_ARG);
-  DYB_REQUIRE(ws_bytes >= dyb_render_scenes_workspace_bytes(nmeshes, V, F), DYB_ERR_WORKSPACE);
   // with no mesh the colours may be NULL; the tile kernel then never reads a colour
-  return render_launch(tab, nscenes, nmeshes, faces, adj_ptr, adj_idx, cam, colors, 0.f, 0.f, 0.f, nullptr, V, F, (flags & 1) ? 0 : 1, ws, st);
+  return render_checked_launch(tab, nscenes, nmeshes, faces, adj_ptr, adj_idx, cam, colors, 0.f, 0.f, 0.f, nullptr, V, F,
+                               (flags & 1) ? 0 : 1, ws, ws_bytes, dyb_render_scenes_workspace_bytes(nmeshes, V, F), opts, st);
+}
+extern "C" int dyb_render_scenes(const dyb_render_scene* scenes, int nscenes, const float* const* mesh_verts, const int* mesh_scene,
+                                 const float* cam, const float* colors, const int* faces, const int* adj_ptr, const int* adj_idx,
+                                 int nmeshes, int V, int F, int flags, void* ws, size_t ws_bytes, hipStream_t st) {
+  return dyb_render_scenes_opt(scenes, nscenes, mesh_verts, mesh_scene, cam, colors, faces, adj_ptr, adj_idx, nmeshes, V, F, flags, ws,
+                               ws_bytes, st, nullptr);
 }

@@ -563,6 +563,37 @@ size_t dyb_render_scenes_workspace_bytes(int nmeshes, int V, int F);
 int dyb_render_scenes(const dyb_render_scene* scenes, int nscenes, const float* const* mesh_verts, const int* mesh_scene,
                       const float* cam, const float* colors, const int* faces, const int* adj_ptr, const int* adj_idx, int nmeshes,
                       int V, int F, int flags, void* ws, size_t ws_bytes, dyb_stream_t stream);
+/* Side views and wireframe: the three entries again with one more argument, opts (HOST; NULL = the plain entry, which forwards here).
+ * model: DEVICE array [meshes][9] fp32, one row-major 3x3 matrix per mesh of the call (NULL: identity), applied to the mesh in the
+ * raw model space of these entries - x' = (m0 x + m1 y) + m2 z, likewise y', z', one rounding per operation - before anything reads
+ * a position: normals, face set-up, depth and shading.  The reference's side view (render_demo.py:96-98: the mesh turned by Rx,
+ * 180 degrees about X, then by R(angle, axis)) is model = Rx R Rx, as Rx is folded into the image coordinates here.  A call with
+ * matrices equals, byte for byte, the plain call on the output of dyb_render_transform_verts (model NULL there: a copy).  It needs
+ * dyb_render_model_workspace_bytes(meshes, V) MORE workspace than its entry's own size (the turned rows lie behind it) and, to check
+ * the matrices before it launches anything, copies them to the host and waits for the stream: DYB_ERR_ARG for an entry that is
+ * not finite, nothing written.  (Hence no stream capture with matrices; calls without matrices never wait.)
+ * wireframe != 0: a face gives a fragment at a pixel centre iff the centre is inside it by the coverage rule AND for at least one
+ * of its edges e  w_e < 256 max(|dx_e|, |dy_e|)  (w_e: the non-negative int64 edge function at the centre, dx_e / dy_e: the edge's
+ * snapped extents in 1/256 pixel): the centre is within one pixel of the edge along its minor axis.  Nearest fragment wins (ties:
+ * lower face index), depth and shading as for the solid mesh; a pixel without a fragment keeps the frame, or falls through to the
+ * mesh beneath in a scene, with face_id -1 and depth +inf - OpenGL's line polygon mode (RenderFlags.ALL_WIREFRAME): only line
+ * fragments take part in the depth test.  Unpinned against pyrender, like the shading. */
+typedef struct dyb_render_opts {
+  const float* model;
+  int wireframe;
+} dyb_render_opts;
+size_t dyb_render_model_workspace_bytes(int N, int V);
+int dyb_render_transform_verts(const float* verts, const float* model, float* out, int N, int V, dyb_stream_t stream);
+int dyb_render_meshes_opt(const float* verts, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
+                          const uint8_t* background, float col_r, float col_g, float col_b, uint8_t* out, int* face_id,
+                          float* depth, int N, int V, int F, int H, int W, void* ws, size_t ws_bytes, dyb_stream_t stream,
+                          const dyb_render_opts* opts);
+int dyb_render_meshes_var_opt(const dyb_render_desc* desc, const int* faces, const int* adj_ptr, const int* adj_idx, const float* cam,
+                              float col_r, float col_g, float col_b, int N, int V, int F, int flags, void* ws, size_t ws_bytes,
+                              dyb_stream_t stream, const dyb_render_opts* opts);
+int dyb_render_scenes_opt(const dyb_render_scene* scenes, int nscenes, const float* const* mesh_verts, const int* mesh_scene,
+                          const float* cam, const float* colors, const int* faces, const int* adj_ptr, const int* adj_idx, int nmeshes,
+                          int V, int F, int flags, void* ws, size_t ws_bytes, dyb_stream_t stream, const dyb_render_opts* opts);
 
 /* ---- native frame stepper: Adaptor.adaptation (reference dynaboa_benchmark.py:126-193) as ONE call per frame --------
  * The first-order bilevel schedule with the frame-loss set - clone, inner_step x [lower-level loss
