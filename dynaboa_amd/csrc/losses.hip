@@ -11,6 +11,7 @@
 // reference away from the theta -> 0 singularity (where autograd itself produces inf*0).
 #include "dyb_common.h"
 #include "dyb_dual.h"
+#include "dyb_gmm.h"
 
 #define NJ 24
 #define NJ49 49
@@ -383,39 +384,11 @@ extern "C" int dyb_perspective_projection_bwd(const float* points, const float* 
 __global__ __launch_bounds__(256) void gmm_prior_kernel(const float* __restrict__ pose, const float* __restrict__ means,
                                                         const float* __restrict__ prec, const float* __restrict__ logw,
                                                         float* __restrict__ out, float* __restrict__ dpose) {
-  __shared__ float sD[NG][ND], sRow[NG][ND], sCol[NG][ND], sQ[NG];
-  __shared__ int sBest;
+  __shared__ DybGmmShared S;
   const int b = blockIdx.x, t = threadIdx.x;
-  for (int i = t; i < NG * ND; i += 256) sD[i / ND][i % ND] = pose[(size_t)b * ND + i % ND] - means[i];
-  __syncthreads();
-  for (int i = t; i < NG * ND; i += 256) {
-    const int m = i / ND, k = i % ND;
-    const float* P = prec + (size_t)m * ND * ND;
-    float r = 0.f, c = 0.f;
-    for (int j = 0; j < ND; ++j) {
-      const float d = sD[m][j];
-      r += P[k * ND + j] * d;
-      c += P[j * ND + k] * d;
-    }
-    sRow[m][k] = r;
-    sCol[m][k] = c;
-  }
-  __syncthreads();
-  if (t < NG) {
-    float q = 0.f;
-    for (int k = 0; k < ND; ++k) q += sRow[t][k] * sD[t][k];
-    sQ[t] = 0.5f * q - logw[t];
-  }
-  __syncthreads();
-  if (t == 0) {
-    int best = 0;
-    for (int m = 1; m < NG; ++m)
-      if (sQ[m] < sQ[best]) best = m;
-    sBest = best;
-    out[b] = sQ[best];
-  }
-  __syncthreads();
-  if (dpose && t < ND) dpose[(size_t)b * ND + t] = 0.5f * (sRow[sBest][t] + sCol[sBest][t]);
+  dyb_gmm_eval<256>(pose + (size_t)b * ND, means, prec, logw, S, t);     // (dyb_gmm.h: shared with the SMPLify body loss)
+  if (t == 0) out[b] = S.Q[S.best];
+  if (dpose && t < ND) dpose[(size_t)b * ND + t] = dyb_gmm_grad(S, t);
 }
 extern "C" int dyb_gmm_prior(const float* pose69, const float* gmm_means, const float* gmm_prec, const float* gmm_logw, float* out,
                              float* dpose69, int B, hipStream_t st) {

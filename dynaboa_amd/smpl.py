@@ -68,14 +68,37 @@ class _LBSFunction(torch.autograd.Function):
         return dbetas, drot, None
 
 
-def _rodrigues(rv: torch.Tensor) -> torch.Tensor:
-    """smplx.lbs.batch_rodrigues (angle = ||r + 1e-8||) in one launch.  Only the metric path converts
-    the ground-truth axis-angle pose (reference dynaboa_benchmark.py:221-227); no gradient."""
-    rv = rv.detach().contiguous().float()
+def _rodrigues_fwd(rv: torch.Tensor) -> torch.Tensor:
     n = rv.shape[0]
     R = torch.empty(n, 3, 3, device=rv.device)
     check(_lib.load().dyb_rodrigues_fwd(rv.data_ptr(), R.data_ptr(), n, stream_of(rv)), "dyb_rodrigues_fwd")
     return R
+
+
+class _Rodrigues(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rv):
+        ctx.in_dtype = rv.dtype
+        rv = rv.contiguous().float()
+        ctx.save_for_backward(rv)
+        return _rodrigues_fwd(rv)
+
+    @staticmethod
+    def backward(ctx, dR):
+        (rv,) = ctx.saved_tensors
+        dR = dR.contiguous().float()
+        d = torch.empty_like(rv)
+        check(_lib.load().dyb_rodrigues_bwd(rv.data_ptr(), dR.data_ptr(), d.data_ptr(), rv.shape[0], stream_of(rv)), "dyb_rodrigues_bwd")
+        return d.to(ctx.in_dtype)                   # the kernel works in float32; the gradient goes back in the input's own dtype
+
+
+def _rodrigues(rv: torch.Tensor) -> torch.Tensor:
+    """smplx.lbs.batch_rodrigues (angle = ||r + 1e-8||) in one launch.  The metric path converts the ground-truth axis-angle
+    pose with it (reference dynaboa_benchmark.py:221-227); an input that requires grad (SMPLify optimises an axis-angle pose)
+    gets the kernel's own backward, dyb_rodrigues_bwd - finite at r = 0.  Forward values are the same either way."""
+    if torch.is_grad_enabled() and rv.requires_grad:
+        return _Rodrigues.apply(rv)
+    return _rodrigues_fwd(rv.detach().contiguous().float())
 
 
 class SMPL(nn.Module):

@@ -753,6 +753,43 @@ int dyb_hmr_backward_train(void* plan, const float* params, const float* acts, c
                            unsigned long long offset, float p, dyb_stream_t stream, dyb_stream_t aux_stream);
 int dyb_hmr_feature_info_ex(const void* plan, int which, int train, long long* offset, int* dims4, int* row_stride);
 
+/* ---- SMPLify (reference utils/smplify/): the optimisation-based fitter on the device (csrc/smplify.hip).  One workgroup per sample,
+ * fixed reduction order; nothing couples the samples of a batch.  kp2d is [B][49][3] = (x, y, confidence) in pixels.
+ * dyb_rodrigues_bwd: the gradient of dyb_rodrigues_fwd exactly as that kernel is written (angle = ||r + 1e-8||, un-normalised axis
+ * r / angle), finite and equal to autograd of the formula at r = 0. */
+int dyb_rodrigues_bwd(const float* axis_angle, const float* drotmat, float* daxis_angle, int n, dyb_stream_t stream);
+/* camera_fitting_loss (utils/smplify/losses.py:83-113; defaults focal 5000, depth_weight 100): loss [B], djoints49 [B][49][3],
+ * dcam_t [B][3].  The OpenPose torso joints are used when all four of their confidences are > 0, else the ground-truth-style ones. */
+int dyb_smplify_camera_loss(const float* joints49, const float* cam_t, const float* cam_t_est, const float* center, const float* kp2d,
+                            float focal, float depth_weight, float* loss, float* djoints49, float* dcam_t, int B, dyb_stream_t stream);
+/* body_fitting_loss (losses.py:49-81; defaults focal 5000, sigma 100, weights 4.78 / 5 / 15.2): parts [B][5] = (reprojection sum,
+ * pose prior, angle prior, shape prior, total), reproj [B][49] (what output='reprojection' returns), total_out [B] (may be NULL);
+ * gradients djoints49 [B][49][3], dpose69 [B][lddp], dbetas [B][lddb], dcam_t [B][3] (may be NULL).  ignore != 0: the five joints of
+ * smplify.py:31 count with confidence 0 (kp2d itself is never written). */
+int dyb_smplify_body_loss(const float* pose69, int ldp, const float* betas, int ldb, const float* joints49, const float* cam_t,
+                          const float* center, const float* kp2d, const float* gmm_means, const float* gmm_prec, const float* gmm_logw,
+                          float focal, float sigma, float pose_prior_weight, float shape_prior_weight, float angle_prior_weight, int ignore,
+                          float* parts, float* reproj, float* total_out, float* djoints49, float* dpose69, int lddp, float* dbetas, int lddb,
+                          float* dcam_t, int B, dyb_stream_t stream);
+/* torch.optim.Adam over the per-sample vector pose 72 | betas 10 | camera 3.  group 1: global orientation + camera (stage 1),
+ * group 2: body pose + betas + global orientation (stage 2).  A gradient is g (+ its *_extra where given).  state (m | v | step
+ * count per sample) is dyb_smplify_adam_state_bytes(B); restart != 0 starts from zero moments and step 0. */
+size_t dyb_smplify_adam_state_bytes(int B);
+int dyb_smplify_adam(float* pose, int ldp, float* betas, int ldb, float* cam_t, const float* dpose, const float* dbody_extra, int lddx,
+                     const float* dbetas, const float* dbetas_extra, int lddbx, const float* dcam_t, void* state, size_t state_bytes,
+                     int group, int restart, double lr, double beta1, double beta2, double eps, int B, dyb_stream_t stream);
+/* SMPLify.__call__ (smplify.py:43-139) in one call on one stream, no host synchronisation: num_iters iterations of the camera loss
+ * over {global orientation, camera}, num_iters of the body loss over {body pose, betas, global orientation} (camera fixed, five
+ * joints ignored), a final forward.  Per iteration: rodrigues, LBS forward, loss head, LBS backward (joints only), rodrigues
+ * backward, Adam.  Outputs verts [B][6890][3], joints49, pose [B][72], betas [B][10], cam_t [B][3], reproj [B][49]; loss_log (may be
+ * NULL) [2 * num_iters][B] per-sample totals, each evaluated before its step.  num_iters = 0 evaluates the initial values.  The
+ * loss weights are the reference's defaults. */
+size_t dyb_smplify_fit_workspace_bytes(int B);
+int dyb_smplify_fit(const float* const* tables_f, const int* const* tables_i, const float* gmm_means, const float* gmm_prec,
+                    const float* gmm_logw, const float* init_pose, const float* init_betas, const float* init_cam_t, const float* center,
+                    const float* kp2d, int num_iters, double lr, float focal, float* verts, float* joints49, float* pose, float* betas,
+                    float* cam_t, float* reproj, float* loss_log, int B, void* ws, size_t ws_bytes, dyb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
