@@ -331,6 +331,9 @@ struct Stepper {
   size_t blob = 0;                    // workspace bytes of ONE replica
   float* in_stage[12] = {};           // staging of the frame inputs, in IN_* order (replica 0): all kinds for nrep > 1; one sequence: only
                                       // the exemplar kinds, and only with an exemplar bank set before the workspace is sized
+  float* in_stage_alt[5] = {};        // replica groups, frame-loss set: the second copy of the first five kinds.  Every call stages into
+                                      // the copy the previous call did not use: a final inference on the side stream ("group_side") keeps
+                                      // reading its own frame
   double lr = 3e-6, beta1 = 0.5, beta2 = 0.9, eps = 1e-8, fastlr = 8e-6, w2d = 10.0, wshape = 2e-6, wpose = 1e-4;
   long long adam_t = 0;
   // caller-owned state and tables (device pointers)
@@ -374,6 +377,7 @@ struct Stepper {
   float *gt_rot = nullptr, *gt_verts[3] = {}, *gt_joints = nullptr, *gt_saved = nullptr, *gt17[2] = {};
   DybEvents* ev = nullptr;
   hipEvent_t e_theta = nullptr, e_side = nullptr, e_gt = nullptr;
+  hipEvent_t e_stage = nullptr;       // replica groups with a side stream: the frame's inputs are staged (on the chain's stream)
   // weight updates by arena ranges beside the next forward ("upd_overlap", replica groups): the fast-weight steps and Adam are
   // streaming passes over [replicas] x 108 MB that nothing overlapped - now the range a forward needs first (stem .. layer2, 5 % of
   // the parameters) is updated on the main stream and the rest (layer3 | layer4 + regressor) on the auxiliary stream while the
@@ -400,6 +404,15 @@ struct Stepper {
   bool defer_pending = false;      // a deferred set has been issued that no consumer has been ordered behind yet
   int n_deferred = 0;              // launches issued behind a backward's join so far (get_f "deferred_launches": what the tests count)
   int upd_late = 1;                // the last range (layer4 + regressor, 68 % of the parameters) is issued when the forward reaches layer3
+  // "group_side" (round 18; replica groups, frame-loss set, with "use_side" and a side stream): the frame's final inference
+  // at the updated weights - a whole forward that nothing on the chain consumes - leaves the chain: frame_step issues forward + record +
+  // result row on the side stream, where they run beside the end of the outer update and the NEXT frame's first level, and the chain's
+  // stream only waits for the update itself (see frame_step; read the outputs behind dyb_stepper_join).  0 = the tail in line, the
+  // issue order of round 8 exactly.  Same kernels, same inputs, same split
+  // depths either way: the results are the same bits.  Measured at 32 sequences, three alternating runs per arm in one session: 502.5 -
+  // 504.0 -> 509.2 - 509.8 frames/s; 8 sequences 276.7 -> 283.8, 64 sequences 556.1 -> 560.9; two groups in one process (six streams on
+  // four hardware queues) lost, 459.4 - 460.7 -> 455.4 - 456.4: the Python handle switches it off there (profiles/r18_group_side_bench.txt).
+  int group_side = 1;
   // one weight update: the fast-weight step out = p - fastlr * g (adam = false), or Adam in place on theta [+ the teacher's EMA]
   struct Upd {
     bool adam = false, ema = false;
@@ -429,6 +442,7 @@ struct Stepper {
   struct GtJob {
     bool on = false;
     const float *pose = nullptr, *betas = nullptr;
+    bool staged = false;           // pose / betas are staged copies written on the chain's stream (e_stage), not the caller's tensors
   } gtjob;
   hipStream_t tail_stream = nullptr;
   std::string err;
@@ -517,6 +531,13 @@ static size_t carve(Stepper& S, char* base) {
     S.in_stage[2] = take_f(B * 72);
     S.in_stage[3] = take_f(B * 10);
     S.in_stage[4] = take_f(B * 2);
+    if (!S.full) {                               // "group_side": the copy the side stream still reads while the next call stages (see adapt)
+      S.in_stage_alt[0] = take_f(B * 3 * (size_t)S.H * S.W);
+      S.in_stage_alt[1] = take_f(B * NJ * 3);
+      S.in_stage_alt[2] = take_f(B * 72);
+      S.in_stage_alt[3] = take_f(B * 10);
+      S.in_stage_alt[4] = take_f(B * 2);
+    }
     if (S.full) {                                // history frame (image, kp2d) and the labelled exemplars (img, kp, pose, betas, pose_3d)
       S.in_stage[5] = take_f(B * 3 * (size_t)S.H * S.W);
       S.in_stage[6] = take_f(B * NJ * 3);
@@ -559,6 +580,7 @@ extern "C" int dyb_stepper_create(void* plan, int B, int H, int W, void** out) {
   if (!S->ev || hipEventCreateWithFlags(&S->e_theta, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&S->e_side, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&S->e_gt, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&S->e_stage, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&S->e_upd, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&S->gates.ev[0], hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&S->gates.ev[1], hipEventDisableTiming) != hipSuccess ||
@@ -578,6 +600,7 @@ extern "C" void dyb_stepper_destroy(void* stepper) {
   if (S->e_theta) (void)hipEventDestroy(S->e_theta);
   if (S->e_side) (void)hipEventDestroy(S->e_side);
   if (S->e_gt) (void)hipEventDestroy(S->e_gt);
+  if (S->e_stage) (void)hipEventDestroy(S->e_stage);
   if (S->e_upd) (void)hipEventDestroy(S->e_upd);
   if (S->gates.ev[0]) (void)hipEventDestroy(S->gates.ev[0]);
   if (S->gates.ev[1]) (void)hipEventDestroy(S->gates.ev[1]);
@@ -786,7 +809,8 @@ static int settle_update(Stepper& S, hipStream_t st);
 static int pass_forward(Stepper& S, Pass& P, const float* theta, const float* image, hipStream_t st, bool chain = true) {
   // (a ranged weight update may still be running on the auxiliary stream: this forward - the first reader of the new weights -
   // waits for each range where it first reads it).  chain = false: a forward on the side stream or a pass stream
-  // - never a consumer of a ranged update (replica groups have no side stream) and it leaves the chain's gate state alone
+  // that must leave the chain's gate state alone (a group's final inference on the side stream IS its update's consuming forward:
+  // frame_step calls it with chain = true)
   const DybFwdGates* gates = (chain && S.gates_pending) ? &S.gates : nullptr;
   {
     const int rc = dyb_hmr_forward_plain(S.plan, theta, image, S.init_state, S.n_iter, P.acts, P.ws, S.ws_bytes, st, gates);
@@ -849,7 +873,7 @@ static int pack_result(Stepper& S, Pass& P, int loss_slot, hipStream_t st) {
   return dyb_result_pack(P.acts + S.off_rot, P.acts + S.off_state, P.verts, row, S.B, st);
 }
 
-// issue what the side stream owes: the previous frame's final forward + record, then this frame's ground-truth meshes
+// issue what the side stream owes: the previous frame's final forward + record (one sequence), then this frame's ground-truth meshes
 static int issue_side_work(Stepper& S, hipStream_t side) {
   if (S.tail.on) {
     HIPOK(hipStreamWaitEvent(side, S.e_theta, 0));
@@ -861,6 +885,7 @@ static int issue_side_work(Stepper& S, hipStream_t side) {
     S.tail.on = false;
   }
   if (S.gtjob.on) {
+    if (S.gtjob.staged) HIPOK(hipStreamWaitEvent(side, S.e_stage, 0));
     RUN(gt_meshes(S, S.gtjob.pose, S.gtjob.betas, side));
     HIPOK(hipEventRecord(S.e_gt, side));
     S.gtjob.on = false;
@@ -1294,12 +1319,19 @@ static int level(Stepper& S, LevelCtx& C, Pass& P, const float* cur, float* nxt,
     // The weight gradients' fused update epilogues (DybWgradUpdateScope, igemm_conv.hip).  Lower level, "fuse_fast": theta_next = cur -
     // fastlr * g straight from the accumulators.  Upper level, "fuse_adam": it is
     // differentiated at the fast weights, so theta has no reader until the final inference - Adam may be applied layer by layer as the
-    // weight gradients finish (replica groups: no side stream whose tail would still read theta)
+    // weight gradients finish (replica groups; a previous frame's tail on the side stream is waited for first)
     S.fused_spans.clear();
     DybWgradUpdate upd{};
     if (fused_epilogues(S) && !upper && S.fuse_fast && S.theta_fast2) {
       upd = DybWgradUpdate{S.grads, S.n_params * sizeof(float), cur, nxt, (float)S.fastlr, &S.fused_spans};
-    } else if (fused_epilogues(S) && upper && S.fuse_adam && cur != S.theta && !C.side && S.nrep > 1) {
+    } else if (fused_epilogues(S) && upper && S.fuse_adam && cur != S.theta && S.nrep > 1) {
+      // ("group_side") the previous frame's final inference may still read theta on the side stream: every writer of theta, the moments and
+      // adam_sc below is on `st` or ordered behind it - the auxiliary stream's weight gradients wait for per-block events recorded on
+      // `st` behind this point, the deferred set is issued behind them on the same in-order stream
+      if (S.side_pending) {
+        HIPOK(hipStreamWaitEvent(st, S.e_side, 0));
+        S.side_pending = false;
+      }
       RUN(adam_prepare(S, st));
       upd = DybWgradUpdate{S.grads, S.n_params * sizeof(float), S.theta, S.theta, 0.f, &S.fused_spans};
       upd.adam_m = S.adam_m; upd.adam_v = S.adam_v; upd.adam_sc = S.adam_sc;
@@ -1444,6 +1476,8 @@ static int frame_step(Stepper& S, LevelCtx& C, int record_slot, int loss_slot, i
   DYB_REQUIRE(!metrics || (C.in[IN_GT_POSE] && C.in[IN_GT_BETAS] && C.in[IN_GENDER]), DYB_ERR_ARG);
   S.out_in_main = false;                                  // this frame's final inference goes to `fin` (reset at every entry point)
   if (!S.use_side || side == st) side = nullptr;
+  // a tail owed by a call that had a side stream, and none now: nobody would issue it before this frame's update rewrites theta
+  if (!side && (S.tail.on || S.gtjob.on) && S.tail_stream && S.tail_stream != st) RUN(issue_side_work(S, S.tail_stream));
   const float* image = (const float*)C.in[IN_IMAGE];
   const long long* gender = (const long long*)C.in[IN_GENDER];
   const int K = S.inner_step;
@@ -1458,7 +1492,12 @@ static int frame_step(Stepper& S, LevelCtx& C, int record_slot, int loss_slot, i
     // tail (which still reads the buffers) - both are issued below, once this frame's first level is in the main queue
     if (side) {
       S.gtjob.on = true; S.gtjob.pose = (const float*)C.in[IN_GT_POSE]; S.gtjob.betas = (const float*)C.in[IN_GT_BETAS];
+      S.gtjob.staged = S.nrep > 1;
     } else {
+      if (S.side_pending) {                      // (the option was switched off between two frames) the last tail's record still reads them
+        HIPOK(hipStreamWaitEvent(st, S.e_side, 0));
+        S.side_pending = false;
+      }
       RUN(gt_meshes(S, (const float*)C.in[IN_GT_POSE], (const float*)C.in[IN_GT_BETAS], st));
     }
   }
@@ -1488,9 +1527,42 @@ static int frame_step(Stepper& S, LevelCtx& C, int record_slot, int loss_slot, i
       HIPOK(hipStreamWaitEvent(st, S.e_side, 0));
       S.side_pending = false;
     }
-    RUN(outer_update(S, st, side ? nullptr : aux));
+    RUN(outer_update(S, st, (side && S.nrep == 1) ? nullptr : aux));
     // final inference() with the updated weights (dynaboa_benchmark.py:156): in line, or - with a side stream - owed to the
     // next call / dyb_stepper_join (the caller keeps this frame's inputs alive until then)
+    if (side && S.nrep > 1) {
+      // "group_side": the final inference leaves the chain for the side stream, issued HERE, under this frame's launch scope and from
+      // this frame's copy of the staged inputs.  Whoever reads theta / the moments on the chain's stream after this call (the caller,
+      // the next frame's first level) must find the whole update done, so the chain's stream waits for every part of it that runs
+      // elsewhere: the last range is issued now rather than from inside a forward, and the waits for the two ranges and the deferred
+      // layer4 / regressor weight gradients are the chain's last commands of the frame.  The side forward is that update's consuming
+      // forward: it takes the gates (behind e_theta: the fused epilogues the backward joined and the first range), so its stem ..
+      // layer3 run while the auxiliary stream finishes, and the rest of it beside the next frame's first level.  Frame f + 1's outer
+      // level waits for e_side before anything writes theta, the moments or adam_sc (level(), outer_update above); its lower levels'
+      // weight gradients write the fast buffers and the gradient arena, never theta.  S.fin shares nothing with the chain or the
+      // auxiliary stream's jobs: its own activation arena, engine workspace (split-K slabs, GroupNorm partials, both conv counter
+      // regions), SMPL outputs and pred17; the ground-truth meshes it reads are written on the side stream itself (gtjob).
+      hipEvent_t done[4] = {nullptr, nullptr, nullptr, nullptr};
+      if (S.gates_pending) {
+        if (S.gates.late) {
+          HIPOK(hipEventRecord(S.gates.mid, st));
+          RUN(late_update(&S));
+        }
+        done[0] = S.gates.ev[0]; done[1] = S.gates.ev[1]; done[2] = S.gates.l4; done[3] = S.gates.reg;
+      }
+      HIPOK(hipEventRecord(S.e_theta, st));
+      for (hipEvent_t e : done)
+        if (e) HIPOK(hipStreamWaitEvent(st, e, 0));
+      HIPOK(hipStreamWaitEvent(side, S.e_theta, 0));
+      RUN(pass_forward(S, S.fin, S.theta, image, side));
+      RUN(settle_update(S, side));                       // (consumed by the forward above; a no-op unless that changes)
+      if (metrics) RUN(record_metrics(S, S.fin, gender, slot++, side));
+      RUN(pack_result(S, S.fin, loss_slot, side));
+      HIPOK(hipEventRecord(S.e_side, side));
+      S.side_pending = true;
+      S.tail_stream = side;
+      return DYB_OK;
+    }
     if (side) {
       HIPOK(hipEventRecord(S.e_theta, st));
       S.tail.on = true; S.tail.image = image; S.tail.gender = gender; S.tail.slot = slot++; S.tail.metrics = metrics;
@@ -1581,9 +1653,15 @@ static int adapt(Stepper& S, const void* const* inputs, int nk, int record_slot,
     for (int k = 0; k < nk; ++k) C.in[k] = inputs[k];
     rc = frame_step(S, C, record_slot, loss_slot, extra, st, aux, side);
   } else {
-    // replicas + side stream: the owed final inference of frame f would read staging buffers the next call has already refilled,
-    // under the next frame's launch scope - replica groups run their tail in line
-    DYB_REQUIRE(!(S.use_side && side && side != st), DYB_ERR_UNSUPPORTED);
+    // replicas + side stream ("group_side"): the final inference of frame f on the side stream must not read staging buffers the next
+    // call has refilled, nor run under the next frame's launch scope.  Frame-loss set: it reads its own copy of the
+    // staged inputs (two copies, used in turn: the copy of frame f is staged into again by frame f + 2, whose chain has waited for
+    // e_side at frame f + 1's outer level).  It is issued by its own call, under its own scope (frame_step).  The full term set and
+    // the dynamic loop keep their tail in line and refuse a side stream.
+    DYB_REQUIRE(!(S.use_side && side && side != st && S.full), DYB_ERR_UNSUPPORTED);
+    if (!S.group_side) side = nullptr;
+    if (S.in_stage_alt[0])
+      for (int k = 0; k < 5; ++k) std::swap(S.in_stage[k], S.in_stage_alt[k]);
     int act[DYB_MAX_REPLICAS];
     const int na = active_set(S, act);
     auto have = [&](int r, int k0, int k1) {
@@ -1602,6 +1680,7 @@ static int adapt(Stepper& S, const void* const* inputs, int nk, int record_slot,
     RUN(make_scope(S, act, na, &R));
     DybRepScope scope(R);
     RUN(stage_inputs(S, inputs, n, IN_IMAGE, 5, st));
+    if (side && side != st) HIPOK(hipEventRecord(S.e_stage, st));      // the side stream's ground-truth meshes read the staged pose / betas
     if (have_hist) RUN(stage_inputs(S, inputs + (size_t)IN_HIST_IMAGE * n, n, IN_HIST_IMAGE, 2, st));
     if (have_ex) RUN(stage_inputs(S, inputs + (size_t)IN_EX_IMG * n, n, IN_EX_IMG, 5, st));
     for (int k = 0; k < nk; ++k) {

@@ -9,11 +9,12 @@
   X(n_iter, "n_iter", nullptr, I, 0, "iterations of the HMR regressor (1 .. 3)")                                                              \
   X(inner_step, "inner_step", nullptr, I, 0, "lower levels per frame (0 .. 16)")                                                              \
   X(eval_lower, "eval_lower", nullptr, I, 0, "a metric record after every inner step")                                                        \
-  X(use_side, "use_side", nullptr, I, 0, "one sequence, frame-loss set: final inference and ground-truth meshes on the side stream")          \
+  X(use_side, "use_side", nullptr, I, 0, "frame-loss set: final inference and ground-truth meshes on the side stream (groups: with group_side)") \
   X(metrics, "metrics", nullptr, I, 0, "metric records at all")                                                                               \
   X(upd_overlap, "upd_overlap", "DYB_UPD_OVERLAP", I, 0, "replica groups: weight updates by arena ranges beside the next forward")            \
   X(upd_late, "upd_late", "DYB_UPD_LATE", I, 0, "the last range (layer4 + regressor) is issued when the consuming forward reaches layer3")    \
   X(wgrad_defer, "wgrad_defer", "DYB_WGRAD_DEFER", I, 0, "layer4 / regressor weight gradients behind the backward's join, beside the next forward") \
+  X(group_side, "group_side", "DYB_GROUP_SIDE", I, 0, "replica groups, frame-loss set: the final inference on the side stream, beside the next frame's first level") \
   X(fuse_fast, "fuse_fast", "DYB_FUSE_FAST", I, 1, "frame-loss set: lower levels' weight gradients write the fast weights themselves (second fast buffer)") \
   X(fuse_adam, "fuse_adam", "DYB_FUSE_ADAM", I, 0, "frame-loss set, replica groups: the outer level's weight gradients apply Adam in place")  \
   X(fuse_ema, "fuse_ema", "DYB_FUSE_EMA", I, 0, "the teacher's EMA inside the Adam pass")                                                     \

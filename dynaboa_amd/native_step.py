@@ -10,6 +10,7 @@ from __future__ import annotations
 import os
 
 import ctypes
+import weakref
 from typing import Dict, Optional
 
 import torch
@@ -124,6 +125,30 @@ class NativeStepper:
                 si("teacher_train", 1)
                 sf("drop_p", float(getattr(adaptor.teacher, "dropout_p", 0.5)))
         self.use_side = 1 if (S == 1 and getattr(adaptor, "_side", None) is not None) else 0
+        # replica groups ("group_side", environment DYB_GROUP_SIDE read when the stepper was created; an adaptor option of that name
+        # wins): the frame's final inference on a side stream of the stepper's own, beside the next frame's first level (read its
+        # outputs behind join()) - main, auxiliary and side are three of the process's four hardware queues.  Frame-loss set only.
+        self._side = None
+        gs = getattr(o, "group_side", None)
+        if gs is not None:
+            si("group_side", int(gs))
+        self.group_side = int(lib.dyb_stepper_get_i(h, b"group_side"))
+        if S > 1 and self.group_side and not self.full:
+            # several groups in one process (bench.py --groups 2: six streams on four hardware queues) measured slower with the side
+            # streams than without (459.4 - 460.7 -> 455.4 - 456.4 frames/s, profiles/r18_group_side_bench.txt): the option is for a
+            # process's ONLY group - a second group's stepper switches it off for itself and for the ones before it
+            import gc
+            if len(_SIDE_GROUPS):
+                gc.collect()                                 # steppers of groups already dropped (adaptor <-> stepper cycles)
+            for other in list(_SIDE_GROUPS):
+                other._group_side_off()
+            if len(_SIDE_GROUPS):
+                self.group_side = 0
+                si("group_side", 0)
+            _SIDE_GROUPS.add(self)
+        if S > 1 and self.group_side and not self.full:
+            self._side = torch.cuda.Stream(device=dev) if dev.type == "cuda" else None
+            self.use_side = 1
         si("use_side", self.use_side)
         for k in ("lr", "beta1", "beta2", "fastlr", "s2dloss_weight", "shape_prior_weight", "pose_prior_weight"):
             sf(k, getattr(o, k))
@@ -287,6 +312,12 @@ class NativeStepper:
         if os.environ.get("DYB_NO_AUX") == "1":      # diagnostic: every launch on the chain's stream (per-kernel durations without company)
             self._aux = None
 
+    def _group_side_off(self):
+        """A further group's stepper was created in this process: back to the in-line tail (C++ reads the option at every frame step)."""
+        if self.group_side and getattr(self, "h", None):
+            check(self.lib.dyb_stepper_set_i(self.h, b"group_side", 0), "set_i group_side")
+            self.group_side = 0
+
     def __del__(self):
         try:
             if getattr(self, "h", None):
@@ -361,7 +392,11 @@ class NativeStepper:
             raise ValueError(f"{self.S} replicas, {len(batches)} batches")
         rows = {r: [b["image"].contiguous().float(), b["smpl_j2d"].contiguous().float()] + self._gt_row(b) for r, b in enumerate(batches)}
         side = None
-        if side_stream is not None and self.use_side:
+        if self.S > 1:
+            # a group's side-stream tail reads the stepper's staged copies of its frame, never the callers' tensors
+            if self.use_side and self._side is not None:
+                side = self._side.cuda_stream
+        elif side_stream is not None and self.use_side:
             side = side_stream.cuda_stream
             for row in rows.values():
                 for t in row:
@@ -504,8 +539,9 @@ class NativeStepper:
         return c[1][r][level]
 
 
+_SIDE_GROUPS = weakref.WeakSet()   # live group steppers with "group_side" on (see NativeStepper.__init__)
 RESULT_RING_ROWS = 2
-BANK_PICK_ROWS = 256           # rows of a sequence's pick log (a ring: a frame draws at most inner_step + 1 + optim_steps times)
+BANK_PICK_ROWS = 256          # rows of a sequence's pick log (a ring: a frame draws at most inner_step + 1 + optim_steps times)
 
 
 # Sequences per launch from which the throughput schedule (dy materialised once per layer by the one-pass GroupNorm backward, plain
@@ -584,6 +620,7 @@ class ReplicaGroup:
         """What the autograd path leaves behind for this step's frames: every sequence's prediction dump, and ALL their overlays
         drawn by one ragged launch (dyb_render_meshes_var) straight from the ring rows."""
         from .base_adaptor import draw_overlays
+        self.stepper.join()                                  # the frame's ring rows are written on the side stream
         jobs = []
         for r in active:
             a, b = self.adaptors[r], batches[r]

@@ -672,8 +672,10 @@ int dyb_stepper_adapt_frame_full(void* stepper, const void* const* inputs, int r
  * ints.  A launch scope holds at most 8 per-replica arenas (workspace, theta, adam_m, adam_v, teacher + the logs): with replicas
  * the four log buffers (records, loss_log, gate_log, feat5_out) must be sub-buffers of ONE per-replica block registered with
  * set_p "logs_base" / set_i "logs_bytes" (replica r's block at logs_base + r * logs_bytes); with separate log pointers the call
- * returns DYB_ERR_UNSUPPORTED rather than alias replicas.  dyb_stepper_adapt_frames (replicas > 1) takes no side stream
- * (DYB_ERR_UNSUPPORTED: the owed final inference would read restaged inputs).  dyb_stepper_set_active: the replicas following
+ * returns DYB_ERR_UNSUPPORTED rather than alias replicas.  dyb_stepper_adapt_frames (replicas > 1) with "use_side" and
+ * "group_side" issues the frame's final inference on `side` itself, from its own copy of the staged inputs, and orders `stream` behind
+ * the whole weight update (read outputs / records / result rows behind dyb_stepper_join); the full term set takes no side stream
+ * (DYB_ERR_UNSUPPORTED).  dyb_stepper_set_active: the replicas following
  * frame steps cover (ascending physical indices; n = 0: all) - sequences of
  * different lengths: a replica whose stream has ended leaves the set, its weights / Adam state / records stay as they are. */
 int dyb_stepper_adapt_frames_full(void* stepper, const void* const* inputs, int record_slot, int loss_slot, int* extra_steps,
