@@ -83,6 +83,21 @@ H36M_TO_J14 = H36M_TO_J17[:14]
 J24_TO_J17 = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 18, 14, 16, 17)
 J24_TO_J14 = J24_TO_J17[:14]
 
+# 3DPW extraction (pw3d_extract.py; reference utils/data_preprocess/pw3d.py:60,71-77).
+# Slots of the 49-joint array that the 18 OpenPose (COCO-18 order) detections of a sequence file go to: BODY_25 without MidHip.
+_COCO18 = ['Nose', 'Neck', 'RShoulder', 'RElbow', 'RWrist', 'LShoulder', 'LElbow', 'LWrist', 'RHip', 'RKnee', 'RAnkle',
+           'LHip', 'LKnee', 'LAnkle', 'REye', 'LEye', 'REar', 'LEar']
+PW3D_OP18_SLOTS = tuple(JOINT_NAMES.index('OP ' + n) for n in _COCO18)
+# The test split's sequence files in the order of the reference's released npz files: the position in this table is the <seq> of
+# 3dpw_<seq>_<pid>.npz, and with it the order of the adapted stream (datasets.key_3dpw).
+PW3D_TEST_ORDER = (
+    'downtown_runForBus_00', 'downtown_rampAndStairs_00', 'flat_packBags_00', 'downtown_runForBus_01', 'office_phoneCall_00',
+    'downtown_windowShopping_00', 'downtown_walkUphill_00', 'downtown_sitOnStairs_00', 'downtown_enterShop_00',
+    'downtown_walking_00', 'downtown_stairs_00', 'downtown_crossStreets_00', 'downtown_car_00', 'downtown_downstairs_00',
+    'downtown_bar_00', 'downtown_walkBridge_01', 'downtown_weeklyMarket_00', 'downtown_warmWelcome_00', 'downtown_arguing_00',
+    'downtown_upstairs_00', 'downtown_bus_00', 'flat_guitar_01', 'downtown_cafe_00', 'outdoors_fencing_01',
+)
+
 # Colours of the tracked people of a scene overlay, 0 .. 255 RGB, indexed by track id modulo the length (render.track_color).
 # Entry 0 is the reference's mesh colour (base_adaptor.py:442).
 TRACK_COLORS = (

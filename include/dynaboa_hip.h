@@ -792,6 +792,18 @@ int dyb_smplify_fit(const float* const* tables_f, const int* const* tables_i, co
                     const float* kp2d, int num_iters, double lr, float focal, float* verts, float* joints49, float* pose, float* betas,
                     float* cam_t, float* reproj, float* loss_log, int B, void* ws, size_t ws_bytes, dyb_stream_t stream);
 
+/* ---- 3DPW extraction (reference utils/data_preprocess/pw3d.py; csrc/pw3d_extract.hip): the annotations of n person-frames in one
+ * launch.  Inputs: joints49 fp32 [n][49][3] (SMPL joints, world coordinates, before translation), trans fp64 [n][3], cam_pose fp64
+ * [n][4][4], cam_intrinsics fp64 [3][3], root_aa fp32 [n][3] (the global orientation as the sequence file stores it).  Outputs:
+ * j2d fp64 [n][49][3] = (u, v, 1) with p = (float)((double)joint + trans) rounded once to fp32 and everything after it in fp64
+ * (q = cam_pose[:3, :] . (p, 1), q /= q.z, uv = (K . q).xy; no special case for q.z <= 0); center fp64 [n][2] and scale fp64 [n] of
+ * the box of the 49 projections (midpoint; max(width, height) / 200); root_aligned fp32 [n][3] =
+ * rotation_matrix_to_angle_axis(fp32(cam_pose[:3, :3]) . batch_rodrigues(root_aa)), both through the quaternion forms of
+ * utils/geometry.py, in fp32.  DYB_ERR_ARG for a null pointer or n <= 0. */
+int dyb_pw3d_annotate(const float* joints49, const double* trans, const double* cam_pose, const double* cam_intrinsics,
+                      const float* root_aa, double* j2d, double* center, double* scale, float* root_aligned, int n,
+                      dyb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
