@@ -14,6 +14,7 @@ from __future__ import annotations
 import argparse
 import os
 import queue
+import re
 import threading
 from typing import Dict, Iterable, Optional
 
@@ -21,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import pose_utils as PU
 from ._abi import check
 from .base_adaptor import BaseAdaptor
 from .hmr import stream_of
@@ -140,6 +142,11 @@ parser.add_argument('--exemplar_bank', type=int, default=0, choices=[0, 1],
                          'retrieves inside the level - no host callback, parallel passes stay on; 0 (default): the reference\'s host retrieval')
 parser.add_argument('--eval_lower', type=int, default=1, choices=[0, 1],
                     help='run inference() after every inner step like the reference (:142)')
+parser.add_argument('--seq_metrics', type=int, default=0, choices=[0, 1],
+                    help='1: besides MPJPE / PA-MPJPE / PVE report the acceleration error, PCK@150mm and AUC of every frame and the means '
+                         'of every sequence (reference utils/pose_utils.py: compute_error_accel, reconstruction_error(needpck, needauc)) - '
+                         'computed at the metric flush by one dyb_seq_metrics call over all frames; forces --deferred_metrics 1 and writes '
+                         '<exppath>/metrics.json and <exppath>/metrics_per_sequence.csv')
 
 
 def frame_only_options(**over):
@@ -191,6 +198,9 @@ class _SideWorker(threading.Thread):
 
 class Adaptor(BaseAdaptor):
     def reset_records(self, nframes: int):
+        if getattr(self.options, "seq_metrics", 0):
+            self.options.deferred_metrics = 1         # the joint sets must stay on the device until the flush
+        self._frame_names = []                         # --seq_metrics 1: the imgname of every frame, for the frame ids
         self.sims, self.feat_sims, self.optim_step_record = [], {}, []
         self.mpjpe_statistics, self.pampjpe_statistics = [[] for _ in range(nframes)], [[] for _ in range(nframes)]
         self.mpjpe_all_lower = [[] for _ in range(self.options.inner_step)]
@@ -262,15 +272,27 @@ class Adaptor(BaseAdaptor):
             t = getattr(m, "theta", None)
         return t
 
-    def excute(self, frames: Optional[Iterable[Dict[str, torch.Tensor]]] = None, nframes: Optional[int] = None):
+    def excute(self, frames: Optional[Iterable[Dict[str, torch.Tensor]]] = None, nframes: Optional[int] = None, seq_lengths=None):
+        """`seq_lengths` (--seq_metrics 1): the frame counts of the stream's sequences; None = the loader's dataset's `sequences`
+        where the stream is that whole dataset (the single-stream parity mode reports per sequence too), else one sequence."""
         frames = self.dataloader if frames is None else frames
         nframes = len(frames) if nframes is None else nframes
         self.reset_records(nframes)
+        seq = bool(getattr(self.options, "seq_metrics", 0))
+        if seq:
+            self._seq_names = getattr(self, "seq_names", None)          # (a caller that knows its sequences' names sets seq_names)
+            ds = getattr(frames, "ds", None)
+            if seq_lengths is None and getattr(ds, "sequences", None) and list(getattr(frames, "indices", ())) == list(range(len(ds))):
+                seq_lengths = [s["frames"] for s in ds.sequences]
+                self._seq_names = [os.path.basename(str(s["file"])) for s in ds.sequences]
+            self._seq_lengths = None if seq_lengths is None else [int(v) for v in seq_lengths]
         mpjpe_all, pampjpe_all, pve_all = [], [], []
         for step, batch in enumerate(frames):
             self.global_step = step
             self.fit_losses = {}
             batch = {k: v.to(self.device) if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
+            if seq:
+                self.note_frame_names(batch)
             self.model.eval()
             mpjpe, pampjpe, pve = self.adaptation(batch)
             self.write_summaries(self.fit_losses)
@@ -280,7 +302,18 @@ class Adaptor(BaseAdaptor):
             self.metric_records = final["records"]          # every inference() of the run, incl. the per-inner-step ones
             mpjpe_all, pampjpe_all, pve_all = final["mpjpe"], final["pampjpe"], final["pve"]
         self.results = dict(mpjpe=mpjpe_all, pampjpe=pampjpe_all, pve=pve_all)
+        if seq:
+            self.results.update({k: final[k] for k in SEQ_KEYS})
+            if getattr(self, "_seq_report", True):
+                write_sequence_report(self.exppath, self.options, self.results)
         return self.results
+
+    def note_frame_names(self, batch):
+        """--seq_metrics 1: remember the frames' imgname (one per sample); the flush reads the frame ids from them."""
+        names = batch.get("imgname")
+        B = int(batch["image"].shape[0])
+        names = [names] if isinstance(names, str) else list(names) if names is not None else []
+        self._frame_names.extend(names if len(names) == B else [None] * B)
 
     # ------------------------------------------------------------------ native frame stepper (csrc/adapt_step.hip)
     def _native_ok(self):
@@ -624,10 +657,67 @@ def check_sync_errors():
                            "set DYB_TP_GN_ONEPASS=1 (single-workgroup slabs only) on a shared or partitioned GPU")
 
 
+def final_selection(rec):
+    """Indices of the records a frame's result is read from: the LAST 'final' record of every step (the dynamic loop appends one
+    per extra step, directly behind each other)."""
+    sel = []
+    for i, r in enumerate(rec):
+        if r['tag'] is not None and r['tag'][0] == 'final':
+            prev = rec[i - 1] if i else None
+            if sel and prev['step'] == r['step'] and prev['tag'] is not None and prev['tag'][0] == 'final':
+                sel[-1] = i
+            else:
+                sel.append(i)
+    return sel
+
+
+SEQ_KEYS = ("accel", "accel_counted", "pck", "auc", "per_sequence")
+_FRAME_ID = re.compile(r"image_(\d+)")
+
+
+def _frame_ids(names, n):
+    """The frames' numbers in their video from their imgname (3DPW: .../image_00042.jpg), or None unless all n names parse."""
+    if names is None or len(names) != n:
+        return None
+    ids = [_FRAME_ID.search(str(x)) if x is not None else None for x in names]
+    return None if any(m is None for m in ids) else [int(m.group(1)) for m in ids]
+
+
+def _sequence_metrics_of(adaptors, recs):
+    """--seq_metrics 1: the last final record of every step of every adaptor, step-major and then batch, through ONE dyb_seq_metrics
+    call; every adaptor is one sequence unless it carries `_seq_lengths`.  -> (frame, seq, parts, lengths): the two device tensors,
+    per adaptor (first frame, frames, first sequence row, names), all sequences' lengths - or None where there is no final record."""
+    pred, gt, lengths, parts, ids, f0 = [], [], [], [], [], 0
+    for k, (a, rec) in enumerate(zip(adaptors, recs)):
+        sel = final_selection(rec)
+        pred += [rec[i]['pred'] for i in sel]
+        gt += [rec[i]['gt'] for i in sel]
+        nf = sum(int(rec[i]['pred'].shape[0]) for i in sel)
+        ln = getattr(a, "_seq_lengths", None) or [nf]
+        if sum(ln) != nf:
+            raise RuntimeError(f"--seq_metrics: sequence lengths {ln} for {nf} frame records")
+        names = getattr(a, "_seq_names", None)
+        if not names or len(names) != len(ln):
+            base = getattr(getattr(a, "options", None), "expname", None) or "sequence"
+            names = [base if len(ln) == 1 and len(adaptors) == 1 else f"{base}_{k}_{j}" for j in range(len(ln))]
+        parts.append((f0, nf, len(lengths), list(names)))
+        lengths += ln
+        ids.append(_frame_ids(getattr(a, "_frame_names", None), nf))
+        f0 += nf
+    if not pred:
+        return None
+    pred, gt = torch.cat(pred), torch.cat(gt)
+    fid = None if any(x is None for x in ids) else torch.tensor([v for x in ids for v in x], dtype=torch.int32)
+    frame, seq = PU.sequence_metrics_device(pred, gt, lengths, frame_id=fid)
+    return frame, seq, parts, lengths
+
+
 def flush_metrics_of(adaptors):
     """`Adaptor.flush_metrics` for several adaptors at once (the sequences of a ReplicaGroup): the deferred records of all of them
     go through ONE Procrustes launch and ONE device->host transfer instead of one of each per adaptor.  -> list of the per-adaptor
-    dicts `flush_metrics` returns."""
+    dicts `flush_metrics` returns.  With --seq_metrics 1 the same transfer also carries the output of one dyb_seq_metrics call and
+    every dict gains SEQ_KEYS: accel (mm) / accel_counted / pck / auc per frame and per_sequence, a list of dicts (name, frames,
+    mpjpe, pampjpe, pck, auc, accel, triples); the other keys and their values are what they are without the flag."""
     for a in adaptors:
         if a._native is not None:
             a._native.join()
@@ -639,6 +729,8 @@ def flush_metrics_of(adaptors):
         recs.append(a._pending)
         a._pending = []
     flat = [r for rec in recs for r in rec]
+    want_seq = bool(adaptors) and bool(getattr(getattr(adaptors[0], "options", None), "seq_metrics", 0))
+    sm = None
     if flat:
         pred = torch.stack([r['pred'] for r in flat])
         gt = torch.stack([r['gt'] for r in flat])
@@ -646,10 +738,18 @@ def flush_metrics_of(adaptors):
         # Procrustes on the device: only scalars cross PCIe (one transfer for the whole run)
         pa_t = pa_mpjpe_device(pred.reshape(n * B, 14, 3), gt.reshape(n * B, 14, 3)).view(n, B)
         allm = torch.cat([torch.stack([r['mpjpe'] for r in flat]).reshape(n, B), pa_t,
-                          torch.stack([r['pve'] for r in flat]).reshape(n, 1)], 1).cpu().numpy() * 1000
+                          torch.stack([r['pve'] for r in flat]).reshape(n, 1)], 1)
+        sm = _sequence_metrics_of(adaptors, recs) if want_seq else None
+        if sm is None:
+            allm = allm.cpu().numpy() * 1000
+        else:
+            host = torch.cat([allm.flatten(), sm[0].flatten(), sm[1].flatten()]).cpu().numpy()
+            k0, k1 = allm.numel(), allm.numel() + sm[0].numel()
+            allm = host[:k0].reshape(n, 2 * B + 1) * 1000
+            frame, seqrows = host[k0:k1].reshape(-1, PU.FRAME_FLOATS), host[k1:].reshape(-1, PU.SEQ_FLOATS)
     check_sync_errors()
     outs, i0 = [], 0
-    for rec in recs:
+    for k, rec in enumerate(recs):
         out = dict(mpjpe=[], pampjpe=[], pve=[], records=[])
         if rec:
             m = allm[i0:i0 + len(rec)]
@@ -657,13 +757,65 @@ def flush_metrics_of(adaptors):
             mp, pa, pve = m[:, :B], m[:, B:2 * B], m[:, 2 * B]
             for i, r in enumerate(rec):
                 out['records'].append(dict(step=r['step'], tag=r['tag'], mpjpe=mp[i], pampjpe=pa[i], pve=float(pve[i])))
-                if r['tag'] is not None and r['tag'][0] == 'final':
-                    if out['mpjpe'] and out['records'][-2]['step'] == r['step'] and out['records'][-2]['tag'][0] == 'final':
-                        out['mpjpe'][-1], out['pampjpe'][-1], out['pve'][-1] = mp[i], pa[i], float(pve[i])
-                    else:
-                        out['mpjpe'].append(mp[i]); out['pampjpe'].append(pa[i]); out['pve'].append(float(pve[i]))
+            for i in final_selection(rec):
+                out['mpjpe'].append(mp[i]); out['pampjpe'].append(pa[i]); out['pve'].append(float(pve[i]))
+        if want_seq:
+            out.update(accel=np.zeros(0, np.float32), accel_counted=np.zeros(0, bool), pck=np.zeros(0, np.float32),
+                       auc=np.zeros(0, np.float32), per_sequence=[])
+            if sm is not None:
+                f0, nf, s0, names = sm[2][k]
+                f = frame[f0:f0 + nf]
+                out.update(accel=f[:, PU.FRAME_ACCEL] * 1000, accel_counted=f[:, PU.FRAME_ACCEL_COUNTED] > 0.5,
+                           pck=f[:, PU.FRAME_PCK].copy(), auc=f[:, PU.FRAME_AUC].copy(),
+                           per_sequence=[sequence_row(nm, seqrows[s0 + j]) for j, nm in enumerate(names)])
         outs.append(out)
     return outs
+
+
+def sequence_row(name, row):
+    """One row of dyb_seq_metrics' per-sequence output (metres) as the report's dict (mm)."""
+    return dict(name=str(name), frames=int(row[PU.SEQ_FRAMES]), mpjpe=float(row[PU.SEQ_MPJPE]) * 1000,
+                pampjpe=float(row[PU.SEQ_PAMPJPE]) * 1000, pck=float(row[PU.SEQ_PCK]), auc=float(row[PU.SEQ_AUC]),
+                accel=float(row[PU.SEQ_ACCEL]) * 1000, triples=int(row[PU.SEQ_TRIPLES]))
+
+
+def sequence_summary(res):
+    """-> (overall, sequence_mean) of a result dict with SEQ_KEYS: the frame-weighted means over all frames (the acceleration error
+    over the counted triples) and the unweighted means over the sequences that have frames (accel: that have a triple)."""
+    flat = lambda x: np.ravel(x).astype(np.float64) if isinstance(x, np.ndarray) else \
+        np.concatenate([np.ravel(np.asarray(v, np.float64)) for v in x]) if len(x) else np.zeros(0)
+    mean = lambda v: float(np.mean(v)) if len(v) else 0.0
+    counted = np.asarray(res["accel_counted"], bool)
+    overall = dict(frames=int(len(res["pck"])), mpjpe=mean(flat(res["mpjpe"])), pampjpe=mean(flat(res["pampjpe"])),
+                   pve=mean(np.ravel(np.asarray(res["pve"], np.float64))), pck=mean(np.asarray(res["pck"], np.float64)),
+                   auc=mean(np.asarray(res["auc"], np.float64)), accel=mean(np.asarray(res["accel"], np.float64)[counted]),
+                   triples=int(counted.sum()))
+    rows = [r for r in res["per_sequence"] if r["frames"] > 0]
+    seq_mean = {k: mean([r[k] for r in rows]) for k in ("mpjpe", "pampjpe", "pck", "auc")}
+    seq_mean["accel"] = mean([r["accel"] for r in rows if r["triples"] > 0])
+    return overall, seq_mean
+
+
+def write_sequence_report(exppath, options, res):
+    """<exppath>/metrics.json (overall frame-weighted means, the mean over sequences, the flags of the run) and
+    <exppath>/metrics_per_sequence.csv (one line per sequence, worst PA-MPJPE first)."""
+    import json
+    os.makedirs(exppath, exist_ok=True)
+    overall, seq_mean = sequence_summary(res)
+    flags = {k: v for k, v in sorted(vars(options).items()) if isinstance(v, (int, float, str, bool, type(None)))}
+    with open(os.path.join(exppath, "metrics.json"), "w") as f:
+        json.dump(dict(overall=overall, sequence_mean=seq_mean, sequences=len(res["per_sequence"]), flags=flags), f, indent=1)
+    cols = ("name", "frames", "mpjpe", "pampjpe", "pck", "auc", "accel", "triples")
+    with open(os.path.join(exppath, "metrics_per_sequence.csv"), "w") as f:
+        f.write(",".join(cols) + "\n")
+        for r in sorted(res["per_sequence"], key=lambda r: -r["pampjpe"]):
+            f.write(",".join(str(r[c]) for c in cols) + "\n")
+    return overall, seq_mean
+
+
+def sequence_line(res):
+    overall, _ = sequence_summary(res)
+    return f"ACCEL:{overall['accel']}, PCK:{overall['pck']}, AUC:{overall['auc']}"
 
 
 if __name__ == '__main__':
@@ -675,3 +827,5 @@ if __name__ == '__main__':
         adaptor = Adaptor(options)
         res = adaptor.excute()
         print(f"MPJPE:{np.mean(res['mpjpe'])}, PAMPJPE:{np.mean(res['pampjpe'])}, PVE:{np.mean(res['pve'])}")
+        if options.seq_metrics:
+            print(sequence_line(res))

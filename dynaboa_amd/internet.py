@@ -265,6 +265,13 @@ def _make_parser():
 parser = _make_parser()
 
 
+def refuse_seq_metrics(options):
+    """--seq_metrics comes with the benchmark driver's parser, but an internet video has no 3-D ground truth to measure against."""
+    if getattr(options, "seq_metrics", 0):
+        raise ValueError("--seq_metrics 1 needs 3-D ground truth (MPJPE, PCK / AUC and the acceleration error are errors against it): "
+                         "internet videos have none - run it with --dataset 3dpw through dynaboa_amd.benchmark")
+
+
 class Adaptor(DB.Adaptor):
     """reference dynaboa_internet.py:69-164: per frame adaptation (the benchmark's schedule: lower levels, upper level, teacher,
     dynamic loop) and then ONE inference without ground truth - no metrics; its products are ``result/Pred_{n}.pt`` (``verts``,
@@ -275,6 +282,7 @@ class Adaptor(DB.Adaptor):
     benchmark driver's branch (one loss, one Adam step, on the autograd path)."""
 
     def __init__(self, options, assets_bundle=None, device=None):
+        refuse_seq_metrics(options)
         options = copy.copy(options)          # the switches below are this adaptor's, not the caller's namespace's
         options.dataset = 'internet'
         options.metrics, options.eval_lower, options.deferred_metrics, options.overlap_metrics = 0, 0, 1, 0
@@ -447,6 +455,7 @@ def scene_renderer(assets_bundle, device):
 def run_driver(options, assets_bundle=None, device=None):
     """``python -m dynaboa_amd.internet``: --extract, or the adaptation of <internet_root> - one stream (the reference), or with
     --split_tracks / --seqs_per_gpu / --num_shards the tracks as sequences."""
+    refuse_seq_metrics(options)
     if options.extract:
         return internet_data_extract(options.extract)
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -46,8 +46,12 @@ def run_sharded(options, sequences: Sequence[SequenceSpec], make_adaptor: Callab
     """Adapt this rank's sequences (waves of `seqs_per_gpu` in lockstep) and gather every rank's per-frame errors.
     make_adaptor() -> a fresh dynaboa_amd.benchmark.Adaptor at the base checkpoint.
     -> dict(global_index, mpjpe, pampjpe, pve): arrays over ALL frames of ALL ranks, sorted by global index, plus 'owned'
-    (this rank's sequence indices) and 'frames_local'."""
+    (this rank's sequence indices) and 'frames_local'.  With options.seq_metrics the gathered row is 8 wide (+ accel, accel_counted,
+    pck, auc): the dict gains those arrays and 'per_sequence' (one dict per sequence of the whole stream, in stream order), which
+    every rank recomputes from the gathered rows - no second collective - and rank 0 writes the report files."""
     from . import native_step as NS
+    seqm = bool(getattr(options, "seq_metrics", 0))
+    W = 8 if seqm else 4
     owned = assign_sequences([s.nframes for s in sequences], num_shards)[shard_rank]
     B = int(getattr(options, "batch_size", 1))
     rows: List[np.ndarray] = []                      # (global frame index, mpjpe, pampjpe, pve) per frame
@@ -61,8 +65,10 @@ def run_sharded(options, sequences: Sequence[SequenceSpec], make_adaptor: Callab
         wave = [sequences[i] for i in order[w0:w0 + S]]
         steps = max(-(-s.nframes // B) for s in wave)
         ads = [make_adaptor() for _ in wave]
-        for a in ads:
+        for a, s in zip(ads, wave):
             a.options.deferred_metrics = 1
+            if seqm:
+                a.options.seq_metrics, a._seq_report, a.seq_names = 1, False, [s.name]      # one report, for the whole run (below)
         # several sequences per GPU share one exppath: result files (--native_results 1 with --save_res / --dump_predictions) carry the
         # GLOBAL frame index - unique, and the reference's single-stream numbering.  Naming only: history / motion keep the local step
         number = S > 1 and bool(getattr(ads[0].options, "native_results", 0))
@@ -71,10 +77,13 @@ def run_sharded(options, sequences: Sequence[SequenceSpec], make_adaptor: Callab
                 for k, b in enumerate(seq.frames()):
                     ad._result_step = seq.first + k * B
                     yield b
-            res = ads[0].excute(numbered() if number else wave[0].frames(), nframes=steps)
+            res = ads[0].excute(numbered() if number else wave[0].frames(), nframes=steps, **(dict(seq_lengths=[wave[0].nframes]) if seqm else {}))
             per_seq = [res]
         else:
             grp = NS.ReplicaGroup(ads, steps)
+            if seqm:
+                for a, s in zip(ads, wave):
+                    a._seq_lengths, a._seq_names = None, [s.name]
             its = [iter(s.frames()) for s in wave]
             for step in range(steps):
                 batches = []
@@ -83,6 +92,8 @@ def run_sharded(options, sequences: Sequence[SequenceSpec], make_adaptor: Callab
                     if b is not None:
                         dev = ads[0].device
                         b = {k: v.to(dev) if isinstance(v, torch.Tensor) else v for k, v in b.items()}
+                        if seqm:
+                            ads[len(batches)].note_frame_names(b)
                     batches.append(b)
                 grp.step(batches, step, result_steps=[s.first + step * B for s in wave] if number else None)
             per_seq = grp.flush_metrics()
@@ -95,16 +106,43 @@ def run_sharded(options, sequences: Sequence[SequenceSpec], make_adaptor: Callab
             n = s.nframes
             pve = np.repeat(pve_b, B)[:n] if pve_b.size else np.zeros(n)
             gi = np.arange(s.first, s.first + n, dtype=np.float64)
-            rows.append(np.stack([gi, mp[:n], pa[:n], pve], 1))
+            cols = [gi, mp[:n], pa[:n], pve]
+            if seqm:
+                if len(res["pck"]) != n:
+                    raise RuntimeError(f"sequence {s.name}: {len(res['pck'])} sequence-metric rows for {n} frames")
+                cols += [np.asarray(res[k], np.float64) for k in ("accel", "accel_counted", "pck", "auc")]
+            rows.append(np.stack(cols, 1))
         del ads
-    local = np.concatenate(rows, 0) if rows else np.zeros((0, 4))
+    local = np.concatenate(rows, 0) if rows else np.zeros((0, W))
     dev = torch.device("cuda", torch.cuda.current_device()) if (torch.cuda.is_available() and torch.distributed.is_available()
                                                                   and torch.distributed.is_initialized()
                                                                   and torch.distributed.get_backend(group) == "nccl") else torch.device("cpu")
-    allr = gather_frame_metrics(torch.from_numpy(local).to(dev).flatten(), group).cpu().numpy().reshape(-1, 4)
+    allr = gather_frame_metrics(torch.from_numpy(local).to(dev).flatten(), group).cpu().numpy().reshape(-1, W)
     allr = allr[np.argsort(allr[:, 0], kind="stable")]
-    return dict(global_index=allr[:, 0].astype(np.int64), mpjpe=allr[:, 1], pampjpe=allr[:, 2], pve=allr[:, 3], owned=owned,
-                frames_local=int(local.shape[0]))
+    out = dict(global_index=allr[:, 0].astype(np.int64), mpjpe=allr[:, 1], pampjpe=allr[:, 2], pve=allr[:, 3], owned=owned,
+               frames_local=int(local.shape[0]))
+    if seqm:
+        out.update(accel=allr[:, 4], accel_counted=allr[:, 5] > 0.5, pck=allr[:, 6], auc=allr[:, 7],
+                   per_sequence=per_sequence_from_rows(sequences, allr))
+        if shard_rank == 0:
+            import os
+            from .benchmark import write_sequence_report
+            write_sequence_report(os.path.join(getattr(options, "expdir", "exps"), getattr(options, "expname", "run")), options, out)
+    return out
+
+
+def per_sequence_from_rows(sequences: Sequence[SequenceSpec], allr: np.ndarray) -> List[dict]:
+    """The report's per-sequence dicts from the gathered 8-wide frame rows (global index, mpjpe, pampjpe, pve, accel,
+    accel_counted, pck, auc): means in double over the sequence's frames, the acceleration error over its counted triples."""
+    out = []
+    gi = allr[:, 0]
+    mean = lambda v: float(np.mean(v)) if len(v) else 0.0
+    for s in sequences:
+        r = allr[(gi >= s.first) & (gi < s.first + s.nframes)]
+        c = r[:, 5] > 0.5
+        out.append(dict(name=str(s.name), frames=int(r.shape[0]), mpjpe=mean(r[:, 1]), pampjpe=mean(r[:, 2]), pck=mean(r[:, 6]),
+                        auc=mean(r[:, 7]), accel=mean(r[c, 4]), triples=int(c.sum())))
+    return out
 
 
 def main(options):
@@ -128,4 +166,6 @@ def main(options):
     res = run_sharded(options, seqs, lambda: DB.Adaptor(options, device=dev), nsh, rank, int(options.seqs_per_gpu))
     if rank == 0:
         print(f"frames:{len(res['mpjpe'])} MPJPE:{np.mean(res['mpjpe'])}, PAMPJPE:{np.mean(res['pampjpe'])}, PVE:{np.mean(res['pve'])}")
+        if getattr(options, "seq_metrics", 0):
+            print(DB.sequence_line(res))
     return res

@@ -375,6 +375,39 @@ int dyb_head_grad_combine(const float* g, const float* drot_loss, const float* d
  * thread, so that the metric path ships scalars instead of joint sets.  aligned (optional) receives the aligned prediction. */
 int dyb_pa_mpjpe(const float* pred, const float* gt, float* out, float* aligned, int n, int J, dyb_stream_t stream);
 
+/* Sequence metrics (csrc/seq_metrics.hip; reference utils/pose_utils.py:66-144: compute_pck, reconstruction_error, compute_error_accel)
+ * over n frames cut into n_seq sequences: one launch over the frames, one reduction per sequence, stream ordered, no synchronisation.
+ * pred, gt [n][J][3] in one unit (root-aligned by the caller); seq_offsets [n_seq + 1] on the device, ascending, [0] = 0,
+ * [n_seq] = n (a sequence of length 0 is legal); valid (may be NULL = all valid) [n]: the reference's `vis`; frame_id (may be
+ * NULL) [n]: the frame's number in its video; thresholds [n_thr] on the device, n_thr in 0..64: the AUC thresholds.
+ * frame_out [n][DYB_SEQM_FRAME_FLOATS], the columns below.  PCK = mean_j(|p_j - g_j| < pck_thr) and AUC = the mean of the PCKs over
+ * `thresholds` (0 for n_thr = 0) are taken on the pair as given, NOT after alignment - what the reference computes.  The
+ * acceleration error of centre frame i is mean_j |(p[i-1] - 2 p[i] + p[i+1]) - (g[i-1] - 2 g[i] + g[i+1])|; the triple counts iff its
+ * three frames lie in one sequence, all three are valid and, with frame_id, their ids are f, f + 1, f + 2; otherwise both columns
+ * are 0.  seq_out [n_seq + 1][DYB_SEQM_SEQ_FLOATS]: per sequence the frame count, the means of columns 0..3 over its frames, the
+ * mean acceleration error over its counted triples (0 when none) and their count; row n_seq the same over all frames; an empty
+ * sequence is a row of zeros.  Sums are taken in double in an order fixed by the sequence's length: no floating-point atomics, two
+ * calls return equal bytes, and a sequence's row does not depend on its place in the batch.  DYB_ERR_ARG (nothing written): a NULL
+ * required pointer (pred, gt and frame_out are required when n > 0), J < 3, n < 0, n_seq < 1, n_thr outside 0..64. */
+#define DYB_SEQM_MPJPE 0
+#define DYB_SEQM_PAMPJPE 1          /* the arithmetic of dyb_pa_mpjpe */
+#define DYB_SEQM_PCK 2
+#define DYB_SEQM_AUC 3
+#define DYB_SEQM_ACCEL 4
+#define DYB_SEQM_ACCEL_COUNTED 5    /* 1.0 if the triple centred on the frame counts, else 0.0 (column 4 is then 0.0) */
+#define DYB_SEQM_FRAME_FLOATS 6
+#define DYB_SEQM_SEQ_FRAMES 0
+#define DYB_SEQM_SEQ_MPJPE 1
+#define DYB_SEQM_SEQ_PAMPJPE 2
+#define DYB_SEQM_SEQ_PCK 3
+#define DYB_SEQM_SEQ_AUC 4
+#define DYB_SEQM_SEQ_ACCEL 5
+#define DYB_SEQM_SEQ_TRIPLES 6
+#define DYB_SEQM_SEQ_FLOATS 7
+int dyb_seq_metrics(const float* pred, const float* gt, const int* seq_offsets, int n_seq, const unsigned char* valid,
+                    const int* frame_id, float pck_thr, const float* thresholds, int n_thr, float* frame_out, float* seq_out, int n,
+                    int J, dyb_stream_t stream);
+
 /* ---- flat-arena updates: learn2learn MAML.adapt (call sites dynaboa_benchmark.py:136,140),
  * torch.optim.Adam (base_adaptor.py:126; dynaboa_benchmark.py:149-151), update_teacher
  * (base_adaptor.py:193-201), cal_feature_diff's cosine (:211-219). n = float count, multiple of 4. */
