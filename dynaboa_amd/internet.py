@@ -258,6 +258,11 @@ def _make_parser():
                    help='1: after the adaptation draw every frame once with all its adapted people: scene/<seq>/<frame>.png')
     p.add_argument('--compose_only', type=int, default=0, choices=[0, 1],
                    help='1: no adaptation - only the --scene_overlays pass over the result/Pred_{n}.pt of <expdir>/<expname>')
+    p.add_argument('--smooth_window', type=int, default=0, metavar='H',
+                   help='H > 0: after the adaptation (and with --compose_only 1) smooth every sequence of the dataset over 2 H + 1 frames '
+                        '(dynaboa_amd.smooth.smooth_results): result_smooth/Pred_{n}.pt, and with --scene_overlays 1 scene_smooth/...; '
+                        'a sequence is what the adaptation streams as one - with several people in a video pass --split_tracks 1')
+    p.add_argument('--smooth_sigma', type=float, default=None, help='--smooth_window: sigma of the Gaussian weights in frames (default H / 2)')
     p.set_defaults(dataset='internet', dump_predictions=1, native_results=1)
     return p
 
@@ -387,40 +392,46 @@ def run_tracks(options, dataset: InternetDataset, make_adaptor, num_shards: int 
 SCENE_BATCH = 8              # frames drawn per scene call (a 1920 x 1080 frame and its picture are 6 MB each on the device)
 
 
-def scene_path(exppath: str, imgname: str) -> str:
+def scene_path(exppath: str, imgname: str, out_dir: str = 'scene') -> str:
     """``<exppath>/scene/<seq>/<frame file stem>.png`` for the frame ``<seq>/<file>``."""
-    return os.path.join(exppath, 'scene', os.path.splitext(imgname)[0] + '.png')
+    return os.path.join(exppath, out_dir, os.path.splitext(imgname)[0] + '.png')
 
 
-def scene_meshes(dataset: InternetDataset, exppath: str, rows: Sequence[int], width: int, height: int):
+def scene_meshes(dataset: InternetDataset, exppath: str, rows: Sequence[int], width: int, height: int, result_dir: str = 'result'):
     """The adapted people of ONE frame (`rows`: its rows) as ``Renderer.render_scenes`` takes them, in painter order: [(verts
     (6890, 3) fp32, cam (4,) = (sx, sy, tx, ty) fp32 in the frame, colour)] from ``result/Pred_{n}.pt`` - the crop camera recovered
     from the stored ``cam_t`` (``render.parse_cam``), carried to the frame with the row's box (``convert_crop_cam_to_orig_img``), both
     in float64 and rounded once.  Every person has a camera of their own, so their depths cannot be compared: the order is by
-    apparent size instead - ascending frame scale sx (the apparently smaller person goes underneath), then track id, then row."""
+    apparent size instead - ascending frame scale sx (the apparently smaller person goes underneath), then track id, then row.
+    result_dir: the folder of the dumps (``result_smooth``: the smoothing pass's); a dump that carries ``cam_frame`` - the smoothed
+    frame camera - is drawn under it instead."""
     import joblib
     from .render import convert_crop_cam_to_orig_img, parse_cam, track_color
     people = []
     for n in rows:
-        path = os.path.join(exppath, 'result', f'Pred_{n}.pt')
+        path = os.path.join(exppath, result_dir, f'Pred_{n}.pt')
         if not os.path.isfile(path):
             raise FileNotFoundError(f"scene overlays: row {n} ({dataset.imgnames[n]}, track {int(dataset.tracks[n])}) has no {path}")
         d = joblib.load(path)
         cam = parse_cam(np.asarray(d['cam'], np.float64).reshape(1, 3))
         bbox = np.array([[dataset.centers[n][0], dataset.centers[n][1], float(dataset.scales[n]) * 200]], np.float64)
         ocam = convert_crop_cam_to_orig_img(cam, bbox, width, height)[0].astype(np.float32)
+        if 'cam_frame' in d:
+            ocam = np.asarray(d['cam_frame'], np.float32).reshape(4)
         people.append((float(ocam[0]), int(dataset.tracks[n]), int(n), np.asarray(d['verts'], np.float32).reshape(-1, 3), ocam))
     people.sort(key=lambda p: p[:3])
     return [(v, ocam, track_color(tr)) for _, tr, _, v, ocam in people]
 
 
-def compose_scenes(dataset: InternetDataset, exppath: str, renderer=None, rows: Optional[Sequence[int]] = None) -> List[str]:
+def compose_scenes(dataset: InternetDataset, exppath: str, renderer=None, rows: Optional[Sequence[int]] = None, result_dir: str = 'result',
+                   out_dir: str = 'scene') -> List[str]:
     """One picture per video frame with every adapted person of it: for each distinct ``imgname`` among `rows` (default: the rows
     of the dataset's sequences) the frame is decoded once, its people are read from the written ``result/Pred_{n}.pt``
     (``scene_meshes``: order and colours) and drawn over it by one scene pass (``Renderer.render_scenes``, SCENE_BATCH frames per
     call) -> ``scene/<seq>/<frame file stem>.png``.  A pass over written results, not part of the frame step: tracks in lockstep
     reach a video frame at different steps, and ranks own different people.  renderer: a ``render.Renderer`` with the meshes' face
-    table (default: the SMPL model's, as the per-person overlays use).  -> the written paths, in frame order of first appearance."""
+    table (default: the SMPL model's, as the per-person overlays use).  result_dir / out_dir: the folders read and written instead of
+    ``result`` and ``scene``.  -> the written paths, in frame order of first appearance."""
     from PIL import Image
     if rows is None:
         rows = [r for s in dataset.sequences for r in s["rows"]]
@@ -433,10 +444,11 @@ def compose_scenes(dataset: InternetDataset, exppath: str, renderer=None, rows: 
     for lo in range(0, len(names), SCENE_BATCH):
         part = names[lo:lo + SCENE_BATCH]
         frames = [torch.from_numpy(dataset.read_frame(name)).to(dataset.device) for name in part]
-        scenes = [scene_meshes(dataset, exppath, by_frame[name], int(f.shape[1]), int(f.shape[0])) for name, f in zip(part, frames)]
+        scenes = [scene_meshes(dataset, exppath, by_frame[name], int(f.shape[1]), int(f.shape[0]), result_dir=result_dir)
+                  for name, f in zip(part, frames)]
         scenes = [[(torch.from_numpy(v).to(dataset.device), torch.from_numpy(c).to(dataset.device), col) for v, c, col in sc] for sc in scenes]
         for name, pic in zip(part, renderer.render_scenes(frames, scenes)):
-            path = scene_path(exppath, name)
+            path = scene_path(exppath, name, out_dir)
             os.makedirs(os.path.dirname(path), exist_ok=True)
             Image.fromarray(pic.cpu().numpy()).save(path)
             paths.append(path)
@@ -450,6 +462,51 @@ def scene_renderer(assets_bundle, device):
         return Renderer(orig_img=True, faces=np.asarray(assets_bundle.smpl_neutral["faces"]), device=device)
     from .smpl import SMPL
     return Renderer(orig_img=True, faces=SMPL("data/smpl", create_transl=False).faces, device=device)
+
+
+def frame_ids_of(dataset: InternetDataset, sequences):
+    """Per sequence the rows' frame numbers, parsed from the trailing digits of the image files' stems - or None unless all parse."""
+    import re
+    out = []
+    for rows in sequences:
+        ids = [re.search(r"(\d+)$", os.path.splitext(os.path.basename(str(dataset.imgnames[n])))[0]) for n in rows]
+        if any(m is None for m in ids):
+            return None
+        out.append([int(m.group(1)) for m in ids])
+    return out
+
+
+def smooth_pass(options, dataset: InternetDataset, exppath: str, assets_bundle=None, device=None, rows: Optional[Sequence[int]] = None):
+    """--smooth_window H: ``smooth.smooth_results`` over the dataset's sequences (`rows`: only the sequences all of whose rows are
+    among them) -> ``result_smooth/Pred_{n}.pt`` with the smoothed frame camera as ``cam_frame`` (``parse_cam`` +
+    ``convert_crop_cam_to_orig_img`` on the row's box; the frame's size is read from its file's header, the frame is not decoded) and,
+    with --scene_overlays 1 or --compose_only 1, ``scene_smooth/...`` drawn from them."""
+    from PIL import Image
+    from . import smooth as SM
+    from .render import convert_crop_cam_to_orig_img, parse_cam
+    from .smpl import SMPL
+    if int(getattr(options, "batch_size", 1)) != 1:
+        raise ValueError("--smooth_window reads the dumps of a batch-size-1 run (Pred_{n}.pt = row n): pass --batch_size 1")
+    done = None if rows is None else {int(r) for r in rows}
+    sequences = [list(s["rows"]) for s in dataset.sequences if done is None or all(int(r) in done for r in s["rows"])]
+    smpl = (SMPL(tables=assets_bundle.smpl_neutral) if assets_bundle is not None else SMPL("data/smpl", create_transl=False)).to(device)
+    sizes: Dict[str, tuple] = {}
+
+    def cam_frame(n, d):
+        name = str(dataset.imgnames[n])
+        if name not in sizes:
+            with Image.open(os.path.join(dataset.img_dir, name)) as im:
+                sizes[name] = im.size                                  # (width, height) from the header
+        cam = parse_cam(np.asarray(d['cam'], np.float64).reshape(1, 3))
+        bbox = np.array([[dataset.centers[n][0], dataset.centers[n][1], float(dataset.scales[n]) * 200]], np.float64)
+        return convert_crop_cam_to_orig_img(cam, bbox, sizes[name][0], sizes[name][1])[0].astype(np.float32)
+
+    paths = SM.smooth_results(exppath, sequences, smpl, half_window=int(options.smooth_window), sigma=getattr(options, "smooth_sigma", None),
+                              frame_ids=frame_ids_of(dataset, sequences), cam_frame=cam_frame)
+    if int(getattr(options, "scene_overlays", 0)) or int(getattr(options, "compose_only", 0)):
+        compose_scenes(dataset, exppath, scene_renderer(assets_bundle, device), rows=[n for s in sequences for n in s],
+                       result_dir='result_smooth', out_dir='scene_smooth')
+    return paths
 
 
 def run_driver(options, assets_bundle=None, device=None):
@@ -470,9 +527,16 @@ def run_driver(options, assets_bundle=None, device=None):
     if scene_pass and nsh > 1:
         raise ValueError("--scene_overlays / --compose_only draw the people of ALL ranks into one picture and there are "
                          f"{nsh} shards: run the shards without it, then once more with --compose_only 1 and --num_shards 1")
+    smooth = int(getattr(options, "smooth_window", 0))
+    if smooth and nsh > 1:
+        raise ValueError("--smooth_window smooths whole sequences, written by ALL ranks, and there are "
+                         f"{nsh} shards: run the shards without it, then once more with --compose_only 1 and --num_shards 1")
     if getattr(options, "compose_only", 0):
         ds = InternetDataset(options, device=device)
-        return compose_scenes(ds, exppath, scene_renderer(assets_bundle, device))
+        paths = compose_scenes(ds, exppath, scene_renderer(assets_bundle, device))
+        if smooth:
+            smooth_pass(options, ds, exppath, assets_bundle, device)
+        return paths
     os.makedirs(exppath, exist_ok=True)
     if rank == 0:
         with open(os.path.join(exppath, 'setting.txt'), 'w') as fh:               # dynaboa_internet.py:176-180
@@ -485,6 +549,8 @@ def run_driver(options, assets_bundle=None, device=None):
         ad.excute()
         if scene_pass:
             compose_scenes(ad.dataset, exppath, scene_renderer(assets_bundle, device))
+        if smooth:
+            smooth_pass(options, ad.dataset, exppath, assets_bundle, device)
         return list(range(len(ad.dataset)))
     if S > 1:
         from . import native_step as NS
@@ -493,6 +559,8 @@ def run_driver(options, assets_bundle=None, device=None):
     done = run_tracks(options, ds, lambda: Adaptor(copy.copy(options), assets_bundle, device), nsh, rank, S)
     if scene_pass:
         compose_scenes(ds, exppath, scene_renderer(assets_bundle, device), rows=done)
+    if smooth:
+        smooth_pass(options, ds, exppath, assets_bundle, device, rows=done)
     return done
 
 

@@ -66,6 +66,12 @@ parser.add_argument('--frames', type=str, default=None, help='driver: directory 
 parser.add_argument('--detections', type=str, default=None,
                     help='driver: .npz with imgname and keypoints (N, 25, 3), or a directory of OpenPose *_keypoints.json files')
 parser.add_argument('--out', type=str, default=None, help='driver: output directory')
+parser.add_argument('--one_euro', type=int, default=0, choices=[0, 1],
+                    help="1: a causal One-Euro filter (dynaboa_amd.smooth.OneEuro) over the frames' pose, shape and frame camera: results "
+                         'gain vts_smooth / rotmat_smooth / shape_smooth (and cam_frame_smooth where box and frame size are known)')
+parser.add_argument('--one_euro_min_cutoff', type=float, default=1.0, help='--one_euro 1: cutoff frequency at rest, Hz (lower: smoother)')
+parser.add_argument('--one_euro_beta', type=float, default=0.0, help='--one_euro 1: how fast the cutoff grows with speed (higher: less lag)')
+parser.add_argument('--fps', type=float, default=30.0, help='--one_euro 1: frame rate of the stream')
 
 SCALE_FACTOR = 1.2          # online_adaptation's call of dataprocess (dynaboa_webcam.py:222)
 _REFERENCE_FLAGS = ('seed', 'model_file', 'lr', 'beta1', 'beta2', 'use_boa', 'fastlr', 's2dloss_weight', 'shape_prior_weight',
@@ -136,6 +142,7 @@ class OnlineAdaptor(DB.Adaptor):
             self.basemodel.eval()
         self.reset_records(max(1, self.options.log_frames))
         self.last_extra_steps = 0
+        self.one_euro = make_one_euro(options, 1, self.device)    # None without --one_euro 1; reload() leaves it alone (OneEuro.reset)
 
     def set_dataloader(self):
         self.dataloader = None                    # frames arrive one at a time through online_adaptation()
@@ -191,10 +198,11 @@ class OnlineAdaptor(DB.Adaptor):
         """One frame: crop, adapt, infer.  -> {'vts' (1, 6890, 3), 'cam' (1, 3), 'bbox' (1, 3)} - device tensors, valid until the
         next call - plus 'rotmat' / 'shape' of the same inference, and 'vts_base' / 'cam_base' with test_basemodel."""
         image, kp, bbox = self.dataprocess(frame_u8, kp25, scaleFactor=SCALE_FACTOR)
-        return self.adapt_processed(image, kp, bbox)
+        return self.adapt_processed(image, kp, bbox, frame_size=(int(frame_u8.shape[1]), int(frame_u8.shape[0])))
 
-    def adapt_processed(self, image, kp, bbox=None) -> Dict[str, object]:
-        """online_adaptation behind dataprocess: image (1, 3, 224, 224), kp (1, 49, 3) with the detections in slots 0..24."""
+    def adapt_processed(self, image, kp, bbox=None, frame_size=None) -> Dict[str, object]:
+        """online_adaptation behind dataprocess: image (1, 3, 224, 224), kp (1, 49, 3) with the detections in slots 0..24.
+        frame_size = (width, height) of the frame the box lies in: with --one_euro 1 it is what the frame camera needs."""
         self.fit_losses = {}
         self.kp2dlosses_lower.clear()
         step = self.global_step
@@ -217,6 +225,8 @@ class OnlineAdaptor(DB.Adaptor):
             with torch.no_grad():
                 b_rot, b_shape, b_cam = self.basemodel(image)
                 res.update(vts_base=self.decode_smpl_params(b_rot, b_shape)["vts"], cam_base=b_cam)
+        if self.one_euro is not None:
+            one_euro_results(self.one_euro, [res], [frame_size], self.decode_smpl_params)
         self.write_summaries(self.fit_losses)
         return res
 
@@ -243,16 +253,56 @@ class OnlineAdaptor(DB.Adaptor):
             ns._sync_adam_steps()
 
     # ------------------------------------------------------------------ overlay
-    def render(self, result, frame_u8, base=False):
-        """The mesh of `result` drawn over its frame (render.py; reference utils/webcam_utils.render) -> (H, W, 3) uint8 device tensor."""
+    def render(self, result, frame_u8, base=False, smooth=False):
+        """The mesh of `result` drawn over its frame (render.py; reference utils/webcam_utils.render) -> (H, W, 3) uint8 device tensor.
+        smooth=True (--one_euro 1): the filtered mesh, under the filtered frame camera where the result has one."""
         from .render import convert_crop_cam_to_orig_img
         frame = frame_u8 if torch.is_tensor(frame_u8) else torch.from_numpy(np.ascontiguousarray(frame_u8))
         frame = frame.to(self.device)
         h, w = int(frame.shape[0]), int(frame.shape[1])
-        vts, cam = (result["vts_base"], result["cam_base"]) if base else (result["vts"], result["cam"])
-        ocam = convert_crop_cam_to_orig_img(cam.detach().float(), result["bbox"], w, h)
+        if smooth and base:
+            raise ValueError("render: the base model's mesh is not filtered - smooth or base, not both")
+        if smooth and "vts_smooth" not in result:
+            raise ValueError("render(smooth=True) draws the keys that --one_euro 1 adds to a result: this one has none")
+        vts, cam = (result["vts_base"], result["cam_base"]) if base else (result["vts_smooth" if smooth else "vts"], result["cam"])
+        if smooth and "cam_frame_smooth" in result:
+            ocam = result["cam_frame_smooth"].detach().float()
+        else:
+            ocam = convert_crop_cam_to_orig_img(cam.detach().float(), result["bbox"], w, h)
         color = (100 / 255.0, 100 / 255.0, 200 / 255.0) if base else self.RESULT_COLOR
         return self._renderer(w, h).render(frame, vts.detach()[0], ocam[0], color=color)
+
+
+def make_one_euro(options, n_seq, device):
+    """The filter of --one_euro 1 over `n_seq` sequences (None without the flag): 24 joint rotations, 10 betas and the four
+    channels of the frame camera (sx, sy, tx, ty)."""
+    if not int(getattr(options, "one_euro", 0)):
+        return None
+    from .smooth import OneEuro
+    return OneEuro(n_seq, fps=float(getattr(options, "fps", 30.0)), min_cutoff=float(getattr(options, "one_euro_min_cutoff", 1.0)),
+                   beta=float(getattr(options, "one_euro_beta", 0.0)), J=24, nb=10, nc=4, device=device)
+
+
+def one_euro_results(filt, results, frame_sizes, decode):
+    """One filter step (ONE launch) over the results of all the filter's sequences; every result gains ``rotmat_smooth``,
+    ``shape_smooth``, ``vts_smooth`` and - where its box and frame size are known - ``cam_frame_smooth`` (1, 4).  The filter's camera
+    channels carry the frame camera (``render.convert_crop_cam_to_orig_img``): the crop camera belongs to the frame's own box, which
+    jitters too.  A sequence without box or frame size feeds (s, s, tx, ty) of its crop camera instead and gains no camera key."""
+    from .render import convert_crop_cam_to_orig_img
+    cams, known = [], []
+    for res, size in zip(results, frame_sizes):
+        cam = res["cam"].detach().float()
+        ok = res.get("bbox") is not None and size is not None
+        cams.append(convert_crop_cam_to_orig_img(cam, res["bbox"], size[0], size[1]) if ok else cam[:, [0, 0, 1, 2]])
+        known.append(ok)
+    rot, shape, camf = filt.step(torch.cat([r["rotmat"].detach().reshape(1, 24, 3, 3) for r in results]),
+                                 torch.cat([r["shape"].detach().reshape(1, 10) for r in results]), torch.cat(cams))
+    with torch.no_grad():
+        vts = decode(rot, shape)["vts"]
+    for k, res in enumerate(results):
+        res.update(rotmat_smooth=rot[k:k + 1], shape_smooth=shape[k:k + 1], vts_smooth=vts[k:k + 1])
+        if known[k]:
+            res["cam_frame_smooth"] = camf[k:k + 1]
 
 
 class OnlineGroup:
@@ -266,16 +316,20 @@ class OnlineGroup:
         from . import native_step as NS
         self.adaptors = list(adaptors)
         self.group = NS.ReplicaGroup(self.adaptors, self.adaptors[0]._nframes)
+        # --one_euro 1: ONE filter over all the group's sequences (one launch per step); the adaptors' own filters stay unused
+        self.one_euro = make_one_euro(self.adaptors[0].online_options, len(self.adaptors), self.adaptors[0].device)
 
     def step(self, frames, detections) -> List[Dict[str, object]]:
         """frames[r] / detections[r]: sequence r's frame and BODY_25 detection.  -> one online_adaptation result per sequence."""
         if len(frames) != len(self.adaptors) or len(detections) != len(self.adaptors) or any(
                 f is None or d is None for f, d in zip(frames, detections)):
             raise ValueError("every sequence of a group brings a frame and a detection to every step")
-        return self.step_processed([a.dataprocess(f, d, scaleFactor=SCALE_FACTOR) for a, f, d in zip(self.adaptors, frames, detections)])
+        return self.step_processed([a.dataprocess(f, d, scaleFactor=SCALE_FACTOR) + ((int(f.shape[1]), int(f.shape[0])),)
+                                    for a, f, d in zip(self.adaptors, frames, detections)])
 
     def step_processed(self, items) -> List[Dict[str, object]]:
-        """items[r] = (image (1, 3, 224, 224), kp (1, 49, 3), bbox (1, 3) or None) of sequence r."""
+        """items[r] = (image (1, 3, 224, 224), kp (1, 49, 3), bbox (1, 3) or None) of sequence r, optionally followed by the frame's
+        (width, height) - what --one_euro 1 needs for the frame camera."""
         ads, ns = self.adaptors, self.group.stepper
         if len(items) != len(ads) or any(it is None for it in items):
             raise ValueError("every sequence of a group brings a frame and a detection to every step")
@@ -312,6 +366,8 @@ class OnlineGroup:
                     res.update(vts_base=a.decode_smpl_params(b_rot, b_shape)["vts"], cam_base=b_cam)
             a.write_summaries(a.fit_losses)
             out[r] = res
+        if self.one_euro is not None:
+            one_euro_results(self.one_euro, out, [it[3] if len(it) > 3 else None for it in items], ads[0].decode_smpl_params)
         return out
 
 

@@ -408,6 +408,42 @@ int dyb_seq_metrics(const float* pred, const float* gt, const int* seq_offsets, 
                     const int* frame_id, float pck_thr, const float* thresholds, int n_thr, float* frame_out, float* seq_out, int n,
                     int J, dyb_stream_t stream);
 
+/* Temporal smoothing of a predicted sequence (csrc/smooth.hip; the reference has no smoother - the rules below are the definition, and
+ * tests/smooth_cases.py restates them in fp64 NumPy).  n frames cut into n_seq sequences as for dyb_seq_metrics: seq_offsets
+ * [n_seq + 1] on the device, valid [n] (NULL = all valid), frame_id [n] (NULL = consecutive).  Frames i and i + 1 are LINKED iff both
+ * lie in one sequence, both are valid and, with frame_id, frame_id[i + 1] == frame_id[i] + 1; a RUN is a maximal chain of linked frames.
+ * dyb_smooth_sequences, the non-causal window: weights_host [2 half_window + 1] is HOST memory, read before the launch and passed by
+ * value; weights_host[k + half_window] weighs tap k = -half_window .. half_window.  Only the taps inside the centre's run count.
+ * rotmat [n][J][9], per joint: q_k = the quaternion of R[i + k] (the four-branch formula of csrc/dyb_quat.h); a tap whose quaternion
+ * is not finite is left out; a tap is negated when dot(q_k, q_0) < 0; s = sum_k w_k q_k in fp32, taps in ascending k; the output is
+ * the rotation matrix of s / |s| (the weighted chordal mean) - or the centre's nine floats, copied, when |s|^2 < 1e-12 or the centre's
+ * own quaternion is not finite.  betas [n][nb] and cam [n][nc] (each may be NULL: not smoothed): sum_k w_k x_k / sum_k w_k per channel.
+ * Byte copies of the input: everything when half_window == 0, invalid frames, frames whose run has length 1.  An invalid frame is
+ * never read as a tap.  One launch, no floating-point atomics, an order of operations that depends on the frame's place in its run
+ * alone: two calls return equal bytes and a sequence's output does not depend on where it lies in the batch.  Stream ordered, no
+ * synchronisation.  DYB_ERR_ARG (nothing written): NULL rotmat, rotmat_out, seq_offsets or weights_host with n > 0; betas without
+ * betas_out or cam without cam_out; an output overlapping its input; half_window outside 0 .. DYB_SMOOTH_MAX_HALF_WINDOW; a weight
+ * that is not finite or < 0, or a centre weight that is not > 0; J < 1, n < 0, n_seq < 1, nb < 0 or nc < 0.
+ * dyb_one_euro_step, the causal form: one One-Euro filter step for R sequences in one launch.  state [R][dyb_one_euro_state_floats(J,
+ * nb, nc)]: per row a `started` float, then x-hat (J x 4 quaternion components | nb | nc floats), then dx-hat of the same size; a
+ * zeroed row is a reset filter.  Groups are each joint's quaternion, each beta, each camera scalar.  Per group, x the new sample,
+ * alpha(c) = 1 / (1 + (1 / (2 pi c)) / te): with started == 0, x-hat = x, dx-hat = 0, started is set and the outputs are byte copies
+ * of the inputs; otherwise x is negated if dot(x, x-hat) < 0 (quaternions), dx = (x - x-hat) / te, dx-hat = alpha(d_cutoff) dx +
+ * (1 - alpha(d_cutoff)) dx-hat, cutoff = min_cutoff + beta |dx-hat| (the norm over the group), x-hat = alpha(cutoff) x +
+ * (1 - alpha(cutoff)) x-hat; a quaternion is then normalised, stored normalised, and its rotation matrix is the output.  active [R]
+ * (NULL = all): the state and outputs of a sequence with active == 0 are not touched.  DYB_ERR_ARG (nothing written): a NULL state,
+ * rotmat or rotmat_out with R > 0; nb > 0 without betas and betas_out, nc > 0 without cam and cam_out; an output overlapping its
+ * input; te, min_cutoff or d_cutoff <= 0 or not finite, beta < 0 or not finite; J < 1, R < 0, nb < 0 or nc < 0
+ * (dyb_one_euro_state_floats returns DYB_ERR_ARG for the same sizes). */
+#define DYB_SMOOTH_MAX_HALF_WINDOW 32
+int dyb_smooth_sequences(const float* rotmat, const float* betas, int nb, const float* cam, int nc, const int* seq_offsets, int n_seq,
+                         const unsigned char* valid, const int* frame_id, const float* weights_host, int half_window,
+                         float* rotmat_out, float* betas_out, float* cam_out, int n, int J, dyb_stream_t stream);
+int dyb_one_euro_state_floats(int J, int nb, int nc);
+int dyb_one_euro_step(float* state, const float* rotmat, const float* betas, int nb, const float* cam, int nc,
+                      const unsigned char* active, float te, float min_cutoff, float beta, float d_cutoff, float* rotmat_out,
+                      float* betas_out, float* cam_out, int R, int J, dyb_stream_t stream);
+
 /* ---- flat-arena updates: learn2learn MAML.adapt (call sites dynaboa_benchmark.py:136,140),
  * torch.optim.Adam (base_adaptor.py:126; dynaboa_benchmark.py:149-151), update_teacher
  * (base_adaptor.py:193-201), cal_feature_diff's cosine (:211-219). n = float count, multiple of 4. */
