@@ -500,6 +500,38 @@ class BaseAdaptor:
                                                  faces=self.smpl_neutral.faces, device=self.device)
         return r
 
+    def overlay_sink(self):
+        """What the pictures are written through when --overlay_format jpg or --overlay_video 1 ask for the device JPEG encoder
+        (jpeg.OverlaySink, made at the first call and kept: this adaptor's own - a replica group writes through its first adaptor's);
+        None: PNG files, as ever."""
+        if "_overlay_sink" not in self.__dict__:
+            from .jpeg import sink_for
+            self._overlay_sink = sink_for(self.options, self.device)
+        return self._overlay_sink
+
+    def close_overlays(self):
+        """End this adaptor's videos (the end of its stream, or an exception on its way out); without a sink nothing happens."""
+        close_overlays([self])
+
+    def overlay_videos(self, jobs, name, prefix=None):
+        """One entry per job of ``overlay_jobs(...)`` for the same batch: the video a job's picture is appended to with
+        --overlay_video 1, ``exppath/video/{prefix}_{sequence name}.avi`` - the name the driver gave this adaptor's sequence
+        (``sequence_name``), else the folder of the frame's file, else 'sequence' - and None for a side-view half (it has no picture
+        of its own) or without the flag."""
+        if not int(getattr(self.options, "overlay_video", 0) or 0):
+            return [None] * len(jobs)
+        names = [name] if isinstance(name, str) else (list(name) if name is not None else [])
+        out, i = [], 0
+        for j in jobs:
+            if j[3] is None:
+                out.append(None)
+                continue
+            n = names[i] if i < len(names) else None
+            i += 1
+            seq = getattr(self, "sequence_name", None) or (os.path.basename(os.path.dirname(str(n))) if n else "") or "sequence"
+            out.append(os.path.join(self.exppath, "video", f"{prefix}_{seq}.avi"))
+        return out
+
     def result_step(self):
         """The number this frame's result files carry: `global_step`, unless the driver numbers them otherwise (the sharded driver
         with several sequences per GPU: the global frame index - its adaptors share one exppath)."""
@@ -569,17 +601,30 @@ class BaseAdaptor:
         (s, s, tx, ty).  Vertices, camera and frame stay on the device; only the finished picture comes to the host.
         -> the written paths."""
         # one ragged launch per 64 pictures, whatever their sizes (3DPW mixes 1920x1080 and 1080x1920 frames)
-        return draw_overlays(self.ragged_renderer(), self.overlay_jobs(vts, cam, images, name, bbox, prefix), self.RESULT_COLOR)
+        jobs = self.overlay_jobs(vts, cam, images, name, bbox, prefix)
+        return draw_overlays(self.ragged_renderer(), jobs, self.RESULT_COLOR, sink=self.overlay_sink(),
+                             videos=self.overlay_videos(jobs, name, prefix))
 
     def write_summaries(self, losses):
         self.last_summaries = losses
 
 
-def draw_overlays(renderer, jobs, color):
+def close_overlays(adaptors):
+    """End the videos of these adaptors (a wave of a driver: the group writes through its first adaptor's sink, a lone sequence
+    through its own).  An adaptor that never made a sink - PNG runs, or the stand-ins of the host tests - is passed over."""
+    for a in adaptors:
+        sink = getattr(a, "__dict__", {}).get("_overlay_sink")
+        if sink is not None:
+            sink.close()
+
+
+def draw_overlays(renderer, jobs, color, sink=None, videos=None):
     """Draw overlay jobs (BaseAdaptor.overlay_jobs, of one adaptor or of all sequences of a group's step) - one ragged launch per 64
     meshes, each over its own frame at its own size - and write the PNGs.  A job without a path (a side view) is the right half of
     the job before it: the two are drawn by the same launch (a launch then draws at most 32 people: 64 descriptors) and joined on
-    the device before the one copy to the host.  -> the written paths."""
+    the device before the one copy to the host.  sink (jpeg.OverlaySink; None: PNG through PIL): the joined pictures of a launch go
+    to it in ONE call - JPEG files and / or the sequences' videos, from one device encode; videos: one entry per job
+    (BaseAdaptor.overlay_videos), the video a job's picture is appended to or None.  -> the written paths."""
     from PIL import Image
     paths = []
     lo = 0
@@ -591,13 +636,21 @@ def draw_overlays(renderer, jobs, color):
         models = [j[4] if len(j) > 4 else None for j in part]
         pics = renderer.render_many([j[0] for j in part], [j[1] for j in part], torch.stack([j[2] for j in part]), color=color,
                                     models=models if any(m is not None for m in models) else None)
+        done, names, into = [], [], []
         for k, j in enumerate(part):
             if j[3] is None:
                 continue
             pic = pics[k]
             if k + 1 < len(part) and part[k + 1][3] is None:
                 pic = torch.cat([pic, pics[k + 1]], 1)
-            Image.fromarray(pic.cpu().numpy()).save(j[3])
-            paths.append(j[3])
+            if sink is None:
+                Image.fromarray(pic.cpu().numpy()).save(j[3])
+                paths.append(j[3])
+            else:
+                done.append(pic)
+                names.append(j[3])
+                into.append(videos[lo + k] if videos is not None else None)
+        if done:
+            paths += sink.write(done, names, into)
         lo = hi
     return paths

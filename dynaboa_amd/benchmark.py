@@ -44,6 +44,8 @@ parser.add_argument('--wireframe', type=int, default=0, choices=[0, 1],
                     help='with --save_res 1: draw the overlay (and the side view) as a wireframe')
 parser.add_argument('--save_obj', type=int, default=0, choices=[0, 1],
                     help='with --save_res 1: also write mesh/{prefix}_{n}.obj per frame, the mesh turned by 180 degrees about X')
+from .jpeg import add_arguments as _overlay_arguments       # --overlay_format / --jpeg_* / --overlay_video / --video_fps
+_overlay_arguments(parser)
 parser.add_argument('--lr', type=float, default=3e-6)
 parser.add_argument('--beta1', type=float, default=0.5)
 parser.add_argument('--beta2', type=float, default=0.9)
@@ -287,16 +289,19 @@ class Adaptor(BaseAdaptor):
                 self._seq_names = [os.path.basename(str(s["file"])) for s in ds.sequences]
             self._seq_lengths = None if seq_lengths is None else [int(v) for v in seq_lengths]
         mpjpe_all, pampjpe_all, pve_all = [], [], []
-        for step, batch in enumerate(frames):
-            self.global_step = step
-            self.fit_losses = {}
-            batch = {k: v.to(self.device) if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
-            if seq:
-                self.note_frame_names(batch)
-            self.model.eval()
-            mpjpe, pampjpe, pve = self.adaptation(batch)
-            self.write_summaries(self.fit_losses)
-            mpjpe_all.append(mpjpe); pampjpe_all.append(pampjpe); pve_all.append(pve)
+        try:
+            for step, batch in enumerate(frames):
+                self.global_step = step
+                self.fit_losses = {}
+                batch = {k: v.to(self.device) if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
+                if seq:
+                    self.note_frame_names(batch)
+                self.model.eval()
+                mpjpe, pampjpe, pve = self.adaptation(batch)
+                self.write_summaries(self.fit_losses)
+                mpjpe_all.append(mpjpe); pampjpe_all.append(pampjpe); pve_all.append(pve)
+        finally:
+            self.close_overlays()                              # the stream's videos end with it, also on an exception
         if self.options.deferred_metrics:
             final = self.flush_metrics()
             self.metric_records = final["records"]          # every inference() of the run, incl. the per-inner-step ones

@@ -44,6 +44,7 @@ import torch
 from . import benchmark as DB
 from . import constants as C
 from . import datasets as D
+from .jpeg import sink_for
 
 INTERNET_ROOT = "data/internet_data"             # stands for the reference's config.InternetData_ROOT (--internet_root)
 MIN_SCORE, MIN_HEIGHT, CONF_THRESHOLD = 2.5, 250, 0.3
@@ -357,6 +358,7 @@ def run_tracks(options, dataset: InternetDataset, make_adaptor, num_shards: int 
     global index) - nothing is gathered, every rank writes its own rows' files.  make_adaptor() -> a fresh Adaptor at the base
     checkpoint.  -> the rows this rank adapted, in the order it finished them."""
     from . import native_step as NS
+    from .base_adaptor import close_overlays
     from .sharding import assign_sequences
     seqs = dataset.sequences
     if int(getattr(options, "batch_size", 1)) != 1:
@@ -371,18 +373,24 @@ def run_tracks(options, dataset: InternetDataset, make_adaptor, num_shards: int 
         wave = [seqs[i] for i in order[w0:w0 + S]]
         steps = max(s["frames"] for s in wave)
         ads = [make_adaptor() for _ in wave]
+        for a, s in zip(ads, wave):                       # --overlay_video 1: one video per (file, track), video/Pred_<name>.avi
+            if s.get("file") is not None:
+                a.sequence_name = f"{os.path.splitext(os.path.basename(str(s['file'])))[0]}_track{s['track']}"
         if len(wave) == 1:
             ads[0].number_by_row = True
             ads[0].excute(D.FrameLoader(dataset, batch_size=1, workers=4, indices=wave[0]["rows"]), nframes=steps)
             done += list(wave[0]["rows"])
         else:
             grp = NS.ReplicaGroup(ads, steps)
-            for step, items in enumerate(TrackGroupLoader(dataset, wave, workers=4, batched=batched)):
-                batches, numbers = [None] * len(wave), [0] * len(wave)
-                for si, b in items:
-                    batches[si], numbers[si] = b, int(b["row"][0])
-                grp.step(batches, step, result_steps=numbers)
-                done += [numbers[si] for si, _ in items]
+            try:
+                for step, items in enumerate(TrackGroupLoader(dataset, wave, workers=4, batched=batched)):
+                    batches, numbers = [None] * len(wave), [0] * len(wave)
+                    for si, b in items:
+                        batches[si], numbers[si] = b, int(b["row"][0])
+                    grp.step(batches, step, result_steps=numbers)
+                    done += [numbers[si] for si, _ in items]
+            finally:
+                close_overlays(ads)                       # the tracks' videos stay open across the wave's steps and end with it
             grp.stepper.join()
         del ads
     return done
@@ -424,14 +432,16 @@ def scene_meshes(dataset: InternetDataset, exppath: str, rows: Sequence[int], wi
 
 
 def compose_scenes(dataset: InternetDataset, exppath: str, renderer=None, rows: Optional[Sequence[int]] = None, result_dir: str = 'result',
-                   out_dir: str = 'scene') -> List[str]:
+                   out_dir: str = 'scene', sink=None) -> List[str]:
     """One picture per video frame with every adapted person of it: for each distinct ``imgname`` among `rows` (default: the rows
     of the dataset's sequences) the frame is decoded once, its people are read from the written ``result/Pred_{n}.pt``
     (``scene_meshes``: order and colours) and drawn over it by one scene pass (``Renderer.render_scenes``, SCENE_BATCH frames per
     call) -> ``scene/<seq>/<frame file stem>.png``.  A pass over written results, not part of the frame step: tracks in lockstep
     reach a video frame at different steps, and ranks own different people.  renderer: a ``render.Renderer`` with the meshes' face
     table (default: the SMPL model's, as the per-person overlays use).  result_dir / out_dir: the folders read and written instead of
-    ``result`` and ``scene``.  -> the written paths, in frame order of first appearance."""
+    ``result`` and ``scene``.  sink (jpeg.OverlaySink; None: PNG through PIL): the pictures of a scene call go to it in ONE call - with
+    --overlay_format jpg the same names with the extension .jpg, with --overlay_video 1 also ``<out_dir>/<seq>.avi``, the frames in
+    this order.  -> the written paths, in frame order of first appearance."""
     from PIL import Image
     if rows is None:
         rows = [r for s in dataset.sequences for r in s["rows"]]
@@ -447,11 +457,19 @@ def compose_scenes(dataset: InternetDataset, exppath: str, renderer=None, rows: 
         scenes = [scene_meshes(dataset, exppath, by_frame[name], int(f.shape[1]), int(f.shape[0]), result_dir=result_dir)
                   for name, f in zip(part, frames)]
         scenes = [[(torch.from_numpy(v).to(dataset.device), torch.from_numpy(c).to(dataset.device), col) for v, c, col in sc] for sc in scenes]
-        for name, pic in zip(part, renderer.render_scenes(frames, scenes)):
-            path = scene_path(exppath, name, out_dir)
+        pics = renderer.render_scenes(frames, scenes)
+        targets = [scene_path(exppath, name, out_dir) for name in part]
+        for path in targets:
             os.makedirs(os.path.dirname(path), exist_ok=True)
+        if sink is not None:
+            videos = [os.path.join(exppath, out_dir, (os.path.dirname(name) or "frames") + ".avi") for name in part]
+            paths += sink.write(pics, targets, videos)
+            continue
+        for path, pic in zip(targets, pics):
             Image.fromarray(pic.cpu().numpy()).save(path)
             paths.append(path)
+    if sink is not None:
+        sink.close()
     return paths
 
 
@@ -505,7 +523,7 @@ def smooth_pass(options, dataset: InternetDataset, exppath: str, assets_bundle=N
                               frame_ids=frame_ids_of(dataset, sequences), cam_frame=cam_frame)
     if int(getattr(options, "scene_overlays", 0)) or int(getattr(options, "compose_only", 0)):
         compose_scenes(dataset, exppath, scene_renderer(assets_bundle, device), rows=[n for s in sequences for n in s],
-                       result_dir='result_smooth', out_dir='scene_smooth')
+                       result_dir='result_smooth', out_dir='scene_smooth', sink=sink_for(options, dataset.device))
     return paths
 
 
@@ -533,7 +551,7 @@ def run_driver(options, assets_bundle=None, device=None):
                          f"{nsh} shards: run the shards without it, then once more with --compose_only 1 and --num_shards 1")
     if getattr(options, "compose_only", 0):
         ds = InternetDataset(options, device=device)
-        paths = compose_scenes(ds, exppath, scene_renderer(assets_bundle, device))
+        paths = compose_scenes(ds, exppath, scene_renderer(assets_bundle, device), sink=sink_for(options, device))
         if smooth:
             smooth_pass(options, ds, exppath, assets_bundle, device)
         return paths
@@ -548,7 +566,7 @@ def run_driver(options, assets_bundle=None, device=None):
         ad = Adaptor(options, assets_bundle, device)
         ad.excute()
         if scene_pass:
-            compose_scenes(ad.dataset, exppath, scene_renderer(assets_bundle, device))
+            compose_scenes(ad.dataset, exppath, scene_renderer(assets_bundle, device), sink=sink_for(options, device))
         if smooth:
             smooth_pass(options, ad.dataset, exppath, assets_bundle, device)
         return list(range(len(ad.dataset)))
@@ -558,7 +576,7 @@ def run_driver(options, assets_bundle=None, device=None):
     ds = InternetDataset(options, device=device)
     done = run_tracks(options, ds, lambda: Adaptor(copy.copy(options), assets_bundle, device), nsh, rank, S)
     if scene_pass:
-        compose_scenes(ds, exppath, scene_renderer(assets_bundle, device), rows=done)
+        compose_scenes(ds, exppath, scene_renderer(assets_bundle, device), rows=done, sink=sink_for(options, device))
     if smooth:
         smooth_pass(options, ds, exppath, assets_bundle, device, rows=done)
     return done

@@ -621,16 +621,20 @@ class ReplicaGroup:
         drawn by one ragged launch (dyb_render_meshes_var) straight from the ring rows."""
         from .base_adaptor import draw_overlays
         self.stepper.join()                                  # the frame's ring rows are written on the side stream
-        jobs = []
+        jobs, videos = [], []
         for r in active:
             a, b = self.adaptors[r], batches[r]
             res = self.stepper.result(f, r)
             if getattr(a.options, "dump_predictions", 0):
                 a.dump_prediction(res["vts"], res["cam"], res["rotmat"], res["shape"])
             if getattr(a.options, "save_res", 0):
-                jobs += a.overlay_jobs(res["vts"], res["cam"], b["image"], b.get("imgname"), b.get("bbox"), prefix="Pred")
+                mine = a.overlay_jobs(res["vts"], res["cam"], b["image"], b.get("imgname"), b.get("bbox"), prefix="Pred")
+                jobs += mine
+                videos += a.overlay_videos(mine, b.get("imgname"), prefix="Pred")
         if jobs:
-            draw_overlays(self.adaptors[active[0]].ragged_renderer(), jobs, self.adaptors[active[0]].RESULT_COLOR)
+            # the group's pictures and videos go through ONE sink, its first adaptor's, whichever sequences are still active
+            draw_overlays(self.adaptors[active[0]].ragged_renderer(), jobs, self.adaptors[active[0]].RESULT_COLOR,
+                          sink=self.adaptors[0].overlay_sink(), videos=videos)
 
     def flush_metrics(self):
         from .benchmark import flush_metrics_of

@@ -72,6 +72,8 @@ parser.add_argument('--one_euro', type=int, default=0, choices=[0, 1],
 parser.add_argument('--one_euro_min_cutoff', type=float, default=1.0, help='--one_euro 1: cutoff frequency at rest, Hz (lower: smoother)')
 parser.add_argument('--one_euro_beta', type=float, default=0.0, help='--one_euro 1: how fast the cutoff grows with speed (higher: less lag)')
 parser.add_argument('--fps', type=float, default=30.0, help='--one_euro 1: frame rate of the stream')
+from .jpeg import add_arguments as _overlay_arguments, sink_for      # --overlay_format / --jpeg_* / --overlay_video / --video_fps
+_overlay_arguments(parser)
 
 SCALE_FACTOR = 1.2          # online_adaptation's call of dataprocess (dynaboa_webcam.py:222)
 _REFERENCE_FLAGS = ('seed', 'model_file', 'lr', 'beta1', 'beta2', 'use_boa', 'fastlr', 's2dloss_weight', 'shape_prior_weight',
@@ -404,20 +406,41 @@ def run_driver(options, adaptor: Optional[OnlineAdaptor] = None, assets_bundle=N
     dets = load_detections(options.detections, names)
     ad = adaptor if adaptor is not None else OnlineAdaptor(options, assets_bundle, device)
     os.makedirs(options.out, exist_ok=True)
+    # --overlay_format jpg: Pred_{n}.jpg from the device encoder; --overlay_video 1: Pred.avi beside the pictures (and, with
+    # --one_euro 1, Pred_smooth.avi of the filtered mesh) - either makes the driver draw, as --save_video 1 does
+    sink = sink_for(options, ad.device)
+    video = sink is not None and sink.video
     written = []
-    for n, name in enumerate(names):
-        if name not in dets:
-            continue
-        frame = D.read_image(os.path.join(options.frames, name))
-        res = ad.online_adaptation(frame, dets[name])
-        cam = res["cam"].detach()
-        cam_t = torch.stack([cam[:, 1], cam[:, 2], 2 * C.FOCAL_LENGTH / (C.IMG_RES * cam[:, 0] + 1e-9)], dim=-1)
-        path = os.path.join(options.out, f"Pred_{n}.npz")
-        np.savez(path, verts=res["vts"].detach().cpu().numpy(), cam=cam_t.cpu().numpy(), rotmat=res["rotmat"].cpu().numpy(),
-                 beta=res["shape"].cpu().numpy())
-        written.append(path)
-        if options.save_video:
-            Image.fromarray(ad.render(res, frame).cpu().numpy()).save(os.path.join(options.out, f"Pred_{n}.png"))
+    try:
+        for n, name in enumerate(names):
+            if name not in dets:
+                continue
+            frame = D.read_image(os.path.join(options.frames, name))
+            res = ad.online_adaptation(frame, dets[name])
+            cam = res["cam"].detach()
+            cam_t = torch.stack([cam[:, 1], cam[:, 2], 2 * C.FOCAL_LENGTH / (C.IMG_RES * cam[:, 0] + 1e-9)], dim=-1)
+            path = os.path.join(options.out, f"Pred_{n}.npz")
+            np.savez(path, verts=res["vts"].detach().cpu().numpy(), cam=cam_t.cpu().numpy(), rotmat=res["rotmat"].cpu().numpy(),
+                     beta=res["shape"].cpu().numpy())
+            written.append(path)
+            if sink is None:
+                if options.save_video:
+                    Image.fromarray(ad.render(res, frame).cpu().numpy()).save(os.path.join(options.out, f"Pred_{n}.png"))
+                continue
+            pics, paths, videos = [], [], []
+            if options.save_video or video:
+                pics.append(ad.render(res, frame))
+                paths.append(os.path.join(options.out, f"Pred_{n}.png") if options.save_video else None)
+                videos.append(os.path.join(options.out, "Pred.avi"))
+            if video and "vts_smooth" in res:
+                pics.append(ad.render(res, frame, smooth=True))
+                paths.append(None)
+                videos.append(os.path.join(options.out, "Pred_smooth.avi"))
+            if pics:
+                sink.write(pics, paths, videos)
+    finally:
+        if sink is not None:
+            sink.close()
     return written
 
 

@@ -14,6 +14,7 @@ With N > 1 or S > 1 every sequence starts from the checkpoint - what each has ad
 stream, stated in DESIGN.md 6."""
 from __future__ import annotations
 
+import os
 from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
@@ -50,6 +51,7 @@ def run_sharded(options, sequences: Sequence[SequenceSpec], make_adaptor: Callab
     pck, auc): the dict gains those arrays and 'per_sequence' (one dict per sequence of the whole stream, in stream order), which
     every rank recomputes from the gathered rows - no second collective - and rank 0 writes the report files."""
     from . import native_step as NS
+    from .base_adaptor import close_overlays
     seqm = bool(getattr(options, "seq_metrics", 0))
     W = 8 if seqm else 4
     owned = assign_sequences([s.nframes for s in sequences], num_shards)[shard_rank]
@@ -67,6 +69,8 @@ def run_sharded(options, sequences: Sequence[SequenceSpec], make_adaptor: Callab
         ads = [make_adaptor() for _ in wave]
         for a, s in zip(ads, wave):
             a.options.deferred_metrics = 1
+            # --overlay_video 1: video/{prefix}_{sequence name}.avi (3DPW names its sequences by their .npz files' paths)
+            a.sequence_name = os.path.splitext(os.path.basename(str(s.name)))[0]
             if seqm:
                 a.options.seq_metrics, a._seq_report, a.seq_names = 1, False, [s.name]      # one report, for the whole run (below)
         # several sequences per GPU share one exppath: result files (--native_results 1 with --save_res / --dump_predictions) carry the
@@ -85,17 +89,20 @@ def run_sharded(options, sequences: Sequence[SequenceSpec], make_adaptor: Callab
                 for a, s in zip(ads, wave):
                     a._seq_lengths, a._seq_names = None, [s.name]
             its = [iter(s.frames()) for s in wave]
-            for step in range(steps):
-                batches = []
-                for it in its:
-                    b = next(it, None)
-                    if b is not None:
-                        dev = ads[0].device
-                        b = {k: v.to(dev) if isinstance(v, torch.Tensor) else v for k, v in b.items()}
-                        if seqm:
-                            ads[len(batches)].note_frame_names(b)
-                    batches.append(b)
-                grp.step(batches, step, result_steps=[s.first + step * B for s in wave] if number else None)
+            try:
+                for step in range(steps):
+                    batches = []
+                    for it in its:
+                        b = next(it, None)
+                        if b is not None:
+                            dev = ads[0].device
+                            b = {k: v.to(dev) if isinstance(v, torch.Tensor) else v for k, v in b.items()}
+                            if seqm:
+                                ads[len(batches)].note_frame_names(b)
+                        batches.append(b)
+                    grp.step(batches, step, result_steps=[s.first + step * B for s in wave] if number else None)
+            finally:
+                close_overlays(ads)                        # a sequence's video stays open across the wave's steps and ends with it
             per_seq = grp.flush_metrics()
         for s, res in zip(wave, per_seq):
             mp = np.concatenate([np.ravel(np.asarray(x, np.float64)) for x in res["mpjpe"]]) if len(res["mpjpe"]) else np.zeros(0)
@@ -125,7 +132,6 @@ def run_sharded(options, sequences: Sequence[SequenceSpec], make_adaptor: Callab
         out.update(accel=allr[:, 4], accel_counted=allr[:, 5] > 0.5, pck=allr[:, 6], auc=allr[:, 7],
                    per_sequence=per_sequence_from_rows(sequences, allr))
         if shard_rank == 0:
-            import os
             from .benchmark import write_sequence_report
             write_sequence_report(os.path.join(getattr(options, "expdir", "exps"), getattr(options, "expname", "run")), options, out)
     return out
@@ -148,7 +154,6 @@ def per_sequence_from_rows(sequences: Sequence[SequenceSpec], allr: np.ndarray) 
 def main(options):
     """`python -m dynaboa_amd.benchmark --num_shards N [--shard_rank r] [--seqs_per_gpu S]`; under torchrun the rank / world size come
     from the environment (RANK, WORLD_SIZE, LOCAL_RANK) and the final gather runs over RCCL."""
-    import os
     import torch.distributed as dist
     from . import benchmark as DB
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -664,6 +664,42 @@ int dyb_render_scenes_opt(const dyb_render_scene* scenes, int nscenes, const flo
                           const float* cam, const float* colors, const int* faces, const int* adj_ptr, const int* adj_idx, int nmeshes,
                           int V, int F, int flags, void* ws, size_t ws_bytes, dyb_stream_t stream, const dyb_render_opts* opts);
 
+/* ---- baseline JPEG of device pictures (csrc/jpeg.hip; dynaboa_amd/jpeg.py adds the header, EOI and the Motion-JPEG writer) --------
+ * Up to 64 pictures of any sizes in one call.  desc: HOST table of N entries - rgb [H][W][3] uint8 (device: what the render entries
+ * write), out (device) receives the entropy-coded scan ONLY - stuffed, padded, no markers - of at most `capacity` bytes;
+ * 1 <= H, W <= 8192.  lengths [N] (device, int64) is ALWAYS the number of bytes the scan needs; where lengths[i] > capacity nothing
+ * at or beyond out + capacity is written, that picture's bytes are unspecified and the other pictures are unaffected.  Stream
+ * ordered, no host wait, no allocation: the table and the prefixes of the pictures' block counts travel as kernel arguments (the
+ * table may be reused when the call returns), six launches whatever N.  No atomics: two calls return equal bytes, and a picture's
+ * bytes do not depend on its place or company in the batch.
+ * The arithmetic is libjpeg's, all integer (tests/jpeg_cases.py restates it in NumPy and is pinned to PIL's files):
+ *   colour   Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16,
+ *            Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16, then - 128
+ *   444      every plane repeats its last column and row up to multiples of 8; blocks in the order Y Cb Cr per 8 x 8 MCU
+ *   420      16 x 16 MCUs, Y00 Y01 Y10 Y11 Cb Cr.  Chroma: the full plane repeats its last column up to 16 x MCUs and ONE row if H
+ *            is odd, (a + b + c + d + bias) >> 2 with bias 1 on even output columns and 2 on odd ones, then the DOWNSAMPLED plane
+ *            repeats its last row.  A Y block beyond ceil(W / 8) columns or ceil(H / 8) rows is a dummy: no AC, the quantised DC of
+ *            the block coded just before it
+ *   DCT      the Independent JPEG Group's accurate integer form (13-bit constants, rows then columns, 8 x the true DCT)
+ *   quant    Annex K.1 / K.2 scaled by s = 5000 / Q (Q < 50) or 200 - 2 Q: q = clamp((base s + 50) / 100, 1, 255);
+ *            c -> sign(c) ((|c| + 4 q) / (8 q))
+ *   entropy  the four Annex K.3 tables, zig-zag order, DC differences per component, no restart markers, 1-bits fill the last
+ *            byte, 0x00 behind every 0xFF
+ * ws: dyb_jpeg_workspace_bytes(desc, N, subsampling) bytes (0 for a table the encode call refuses): per block 134 bytes
+ * (coefficients, DC, bit offset), per picture min(capacity, 208 x blocks) bytes of unstuffed stream, 12 bytes per 1024 blocks and
+ * per 1024 worst-case stream bytes.  DYB_ERR_ARG: NULL table, rgb, out or lengths, N < 1, non-positive size, negative capacity,
+ * quality outside 1 .. 100; DYB_ERR_UNSUPPORTED: N > 64, H or W > 8192, subsampling other than 444 or 420; DYB_ERR_WORKSPACE.
+ * Everything is checked before the first launch: nothing is written when an error code is returned. */
+typedef struct dyb_jpeg_desc {
+  const uint8_t* rgb;
+  uint8_t* out;
+  int H, W;
+  long long capacity;
+} dyb_jpeg_desc;
+size_t dyb_jpeg_workspace_bytes(const dyb_jpeg_desc* desc, int N, int subsampling);
+int dyb_jpeg_encode_many(const dyb_jpeg_desc* desc, int N, int quality, int subsampling, long long* lengths, void* ws,
+                         size_t ws_bytes, dyb_stream_t stream);
+
 /* ---- native frame stepper: Adaptor.adaptation (reference dynaboa_benchmark.py:126-193) as ONE call per frame --------
  * The first-order bilevel schedule with the frame-loss set - clone, inner_step x [lower-level loss
  * (base_adaptor.py:222-268) -> learner.adapt -> inference], upper-level loss (:270-317) through the fast weights,

@@ -10,8 +10,10 @@ process, a warm-up, then --frames frame steps per leg; prints one JSON line per 
   part 3  32 meshes over 1920 x 1080 frames: ONE ragged launch (with and without the per-mesh pixel box) against 32 launches of the
           uniform entry, event-timed.  The mesh: tools/render_times.py's ellipsoid with SMPL's counts, or --soup (the synthetic
           SMPL's random-triple faces, hundreds deep at every pixel - the stress case).
+  part 4  --overlay_format png against jpg (the device JPEG encoder of csrc/jpeg.hip): 1 and 32 sequences with --save_res 1 on the
+          native stepper, the two legs alternating over --rounds rounds; median step time with min .. max.
 
-usage:  timeout 900 python tools/native_results_rate.py [--part 1|2|3|all] [--frames 200] [--warmup 10] [--soup]
+usage:  timeout 900 python tools/native_results_rate.py [--part 1|2|3|4|all (= 1 - 3)] [--frames 200] [--warmup 10] [--rounds 3] [--soup]
 """
 import argparse
 import json
@@ -194,9 +196,61 @@ def part3(a):
     print(json.dumps(out), flush=True)
 
 
+def part4(a, clock):
+    """--overlay_format png against jpg, end to end: S sequences in lockstep (S = 1 and --sequences), frame-loss set, native_results 1,
+    save_res 1 over the 224 x 224 crops.  Both groups live side by side and take turns: --rounds rounds of --frames steps each,
+    alternating; the median step time with its spread (min .. max) per leg."""
+    import statistics
+    NS.set_replica_policy(True)
+    base = dict(vars(DB.frame_only_options(inner_step=1)), native_results=1, save_res=1)
+    for S in sorted({1, a.sequences}):
+        frames = [[{k: v.to("cuda:0") for k, v in assets.make_frame(100 * r + i, 1, seed=22).items()} for i in range(4)] for r in range(S)]
+        out = dict(part=4, what=f"{S} sequences, frame-loss set, native_results 1, save_res 1: overlay_format png / jpg",
+                   steps=a.frames, warmup=a.warmup, rounds=a.rounds)
+        with tempfile.TemporaryDirectory() as tmp:
+            legs, at = {}, {}
+            for leg in ("png", "jpg"):
+                ads = [make(dict(base, overlay_format=leg), r, os.path.join(tmp, leg)) for r in range(S)]
+                legs[leg] = NS.ReplicaGroup(ads, a.rounds * a.frames + a.warmup) if S > 1 else ads[0]
+                if S == 1:
+                    ads[0].reset_records(a.rounds * a.frames + a.warmup)
+                at[leg] = 0
+
+            def step(leg):
+                i = at[leg]
+                at[leg] += 1
+                if S > 1:
+                    legs[leg].step([frames[r][i % 4] for r in range(S)], i, result_steps=[i * S + r for r in range(S)])
+                else:
+                    ad = legs[leg]
+                    ad.global_step, ad.fit_losses = i, {}
+                    ad.model.eval()
+                    ad.adaptation(frames[0][i % 4])
+            for leg in legs:
+                for _ in range(a.warmup):
+                    step(leg)
+            torch.cuda.synchronize()
+            times = {leg: [] for leg in legs}
+            for _ in range(a.rounds):
+                for leg in legs:
+                    t0 = time.perf_counter()
+                    for _ in range(a.frames):
+                        step(leg)
+                    torch.cuda.synchronize()
+                    times[leg].append(1e3 * (time.perf_counter() - t0) / a.frames)
+            for leg in legs:
+                n = len(os.listdir(os.path.join(tmp, leg, "rate", "image")))
+                assert n == S * (a.rounds * a.frames + a.warmup), (leg, n)
+                out[leg] = dict(ms_per_step_median=round(statistics.median(times[leg]), 3), ms_min=round(min(times[leg]), 3),
+                                ms_max=round(max(times[leg]), 3))
+            del legs
+        print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", default="all", choices=["1", "2", "3", "all"])
+    ap.add_argument("--part", default="all", choices=["1", "2", "3", "4", "all"], help="all = parts 1 - 3; part 4 only when named")
+    ap.add_argument("--rounds", type=int, default=3, help="part 4: alternating rounds per leg")
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--sequences", type=int, default=32)
@@ -210,6 +264,8 @@ def main():
         part2(a, clock)
     if a.part in ("3", "all"):
         part3(a)
+    if a.part == "4":                                # not part of "all": that stays what it was
+        part4(a, clock)
 
 
 if __name__ == "__main__":
