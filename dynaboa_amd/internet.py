@@ -35,6 +35,7 @@ import copy
 import glob
 import json
 import os
+import re
 from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, Optional, Sequence
 
@@ -88,15 +89,16 @@ def track_of(annot: dict) -> int:
     return -1 if idx is None else int(idx)
 
 
-def internet_data_extract(in_path: str) -> List[str]:
+def internet_data_extract(in_path: str, track: int = 0, device="cuda", **rule) -> List[str]:
     """reference utils/data_preprocess/internet_data.py:42-79: for every ``<seq>.json`` of `in_path` (in name order) keep the
-    detections with score >= 2.5 and person height >= 250 and write ``<seq>.npz``.  -> the files written."""
+    detections with score >= 2.5 and person height >= 250 and write ``<seq>.npz``.  track = 1 (--track 1): the ``track`` array comes
+    from ``tracked_ids`` instead of the records' ``idx``.  -> the files written."""
     seqs = sorted(os.path.basename(n)[:-5] for n in glob.glob(os.path.join(in_path, '*.json')))
-    written = []
+    written, pending = [], []
     for seq in seqs:
         with open(os.path.join(in_path, f'{seq}.json')) as fh:
             annots = json.load(fh)
-        imagenames, scales, centers, j2ds, tracks = [], [], [], [], []
+        imagenames, scales, centers, j2ds, tracks, raw = [], [], [], [], [], []
         for annot in annots:
             kps2d = np.array(annot['keypoints']).reshape(-1, 3)
             if annot['score'] < MIN_SCORE or person_height(kps2d) < MIN_HEIGHT:
@@ -104,16 +106,62 @@ def internet_data_extract(in_path: str) -> List[str]:
             if kps2d.shape != (17, 3):
                 raise ValueError(f"{seq}.json: a detection with {kps2d.shape[0]} joints (COCO-17 expected)")
             center, scale = detection_bbox(kps2d)
+            if track:
+                raw.append(kps2d.astype(np.float32))                    # the raw confidences, before the 0 / 1 rewrite
             kps2d[:, 2] = kps2d[:, 2] > CONF_THRESHOLD
             part = np.zeros([C.NUM_OUT_JOINTS, 3])
             part[list(COCO_TO_49)] = kps2d
             imagenames.append(os.path.join(seq, annot['image_id']))
             centers.append(center); scales.append(scale); j2ds.append(part); tracks.append(track_of(annot))
-        out_file = os.path.join(in_path, f'{seq}.npz')
-        np.savez(out_file, imgname=imagenames, center=centers, scale=scales, part=j2ds, track=np.array(tracks, dtype=np.int64))
-        print(f'{seq}: {len(annots)} detections, {len(imagenames)} kept')
-        written.append(out_file)
+        arrays = dict(imgname=imagenames, center=centers, scale=scales, part=j2ds, track=np.array(tracks, dtype=np.int64))
+        if track:
+            pending.append((seq, len(annots), arrays, raw))              # written below, after the one call over all files
+        else:
+            written.append(_write_extract(in_path, seq, len(annots), arrays))
+    if track:
+        for (_, _, arrays, _), ids in zip(pending, tracked_ids([(p[2]["imgname"], p[3]) for p in pending], device=device, **rule)):
+            arrays["track"] = ids
+        written = [_write_extract(in_path, seq, total, arrays) for seq, total, arrays, _ in pending]
     return written
+
+
+def _write_extract(in_path, seq, total, arrays):
+    out_file = os.path.join(in_path, f'{seq}.npz')
+    np.savez(out_file, **arrays)
+    print(f'{seq}: {total} detections, {len(arrays["imgname"])} kept')
+    return out_file
+
+
+def tracked_ids(videos, device="cuda", **rule) -> List[np.ndarray]:
+    """--extract --track 1.  videos: per file (image names, raw (17, 3) detections) of the rows it keeps, in record order.  A video's
+    frames are its distinct image names in order of first appearance, numbered by the trailing digits of their stems when all of
+    them parse and increase (else by position); ALL videos go into one ``track.track_videos`` call.  -> per file the rows' ids
+    (int64; -1: a detection the rule leaves without a track)."""
+    from . import track as T
+    batch, ids, where = [], [], []
+    for names, raw in videos:
+        frames: Dict[str, List[int]] = {}
+        for row, name in enumerate(names):
+            frames.setdefault(name, []).append(row)                       # dicts keep first-appearance order
+        order, rows_of = list(frames), list(frames.values())
+        num = [re.search(r"(\d+)$", os.path.splitext(os.path.basename(n))[0]) for n in order]
+        fid = None
+        if all(m is not None for m in num) and len({int(m.group(1)) for m in num}) == len(num):
+            by_id = sorted(range(len(order)), key=lambda i: int(num[i].group(1)))     # records out of frame order: the numbers decide
+            rows_of, fid = [rows_of[i] for i in by_id], [int(num[i].group(1)) for i in by_id]
+        batch.append([np.stack([raw[r] for r in rows]) for rows in rows_of])
+        ids.append(fid)
+        where.append(rows_of)
+    if any(x is None for x in ids):
+        ids = None
+    tracks, _, _ = T.track_videos(batch, ids, device=device, **rule)
+    out = []
+    for (names, _), rows_of, per_frame in zip(videos, where, tracks):
+        col = -np.ones(len(names), np.int64)
+        for rows, tr in zip(rows_of, per_frame):
+            col[rows] = tr
+        out.append(col)
+    return out
 
 
 # ---------------------------------------------------------------------------------------- dataset
@@ -250,6 +298,12 @@ def _make_parser():
     p.description = __doc__                 #  change the benchmark driver's own defaults with them)
     p.formatter_class = argparse.RawDescriptionHelpFormatter
     p.add_argument('--extract', type=str, default=None, metavar='DIR', help='write DIR/<seq>.npz for every DIR/<seq>.json and stop')
+    p.add_argument('--track', type=int, default=0, choices=[0, 1],
+                   help="--extract: 1: the track array of every <seq>.npz comes from the device tracker (dynaboa_amd.track: one call "
+                        "over all files, on the detections that pass the score and height filters, with their raw confidences) instead "
+                        "of the records' idx - for AlphaPose output without pose tracking; --c_min ... --min_common set the rule")
+    from .track import add_rule_arguments
+    add_rule_arguments(p)
     p.add_argument('--internet_root', type=str, default=INTERNET_ROOT, help="folder of the <seq>.npz files and images/ (the reference's "
                                                                            'config.InternetData_ROOT)')
     p.add_argument('--split_tracks', type=int, default=0, choices=[0, 1],
@@ -532,7 +586,12 @@ def run_driver(options, assets_bundle=None, device=None):
     --split_tracks / --seqs_per_gpu / --num_shards the tracks as sequences."""
     refuse_seq_metrics(options)
     if options.extract:
-        return internet_data_extract(options.extract)
+        if not int(getattr(options, "track", 0)):
+            return internet_data_extract(options.extract)
+        from .track import rule_of
+        return internet_data_extract(options.extract, track=1, device="cuda" if device is None else device, **rule_of(options))
+    if int(getattr(options, "track", 0)):
+        raise ValueError("--track 1 belongs to --extract DIR: it decides the track array the files are written with")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", options.shard_rank))
     nsh = world if world > 1 else int(options.num_shards)

@@ -72,6 +72,13 @@ parser.add_argument('--one_euro', type=int, default=0, choices=[0, 1],
 parser.add_argument('--one_euro_min_cutoff', type=float, default=1.0, help='--one_euro 1: cutoff frequency at rest, Hz (lower: smoother)')
 parser.add_argument('--one_euro_beta', type=float, default=0.0, help='--one_euro 1: how fast the cutoff grows with speed (higher: less lag)')
 parser.add_argument('--fps', type=float, default=30.0, help='--one_euro 1: frame rate of the stream')
+parser.add_argument('--track', type=int, default=0, choices=[0, 1],
+                    help='driver, with --detections an OpenPose directory: 0: people[0] of every frame; 1: ALL people go through the '
+                         'device tracker (dynaboa_amd.track) and every kept track is adapted on its own, from a fresh adaptation '
+                         'state, into <out>/track<id>/ (the tracks\' detections: <out>/track<id>.npz, <out>/tracks.json)')
+parser.add_argument('--min_track_frames', type=int, default=1, help='--track 1: drop tracks with fewer frames')
+from .track import add_rule_arguments as _rule_arguments             # --c_min / --kappa / --s_min / --max_age / --min_common
+_rule_arguments(parser)
 from .jpeg import add_arguments as _overlay_arguments, sink_for      # --overlay_format / --jpeg_* / --overlay_video / --video_fps
 _overlay_arguments(parser)
 
@@ -403,9 +410,37 @@ def run_driver(options, adaptor: Optional[OnlineAdaptor] = None, assets_bundle=N
     if not (options.frames and options.detections and options.out):
         raise SystemExit("--frames, --detections and --out are required")
     names = sorted(n for n in os.listdir(options.frames) if n.lower().endswith((".png", ".jpg", ".jpeg", ".bmp")))
+    if int(getattr(options, "track", 0)):
+        return run_tracked(options, names, adaptor, assets_bundle, device)
     dets = load_detections(options.detections, names)
     ad = adaptor if adaptor is not None else OnlineAdaptor(options, assets_bundle, device)
-    os.makedirs(options.out, exist_ok=True)
+    return drive_frames(options, names, dets, ad, options.out)
+
+
+def run_tracked(options, names: Sequence[str], adaptor=None, assets_bundle=None, device=None) -> List[str]:
+    """--track 1: the people of an OpenPose directory through ``track.track_openpose`` (-> ``<out>/track<id>.npz``,
+    ``<out>/tracks.json``), then every kept track through ``drive_frames`` with an adaptor of its own - what the driver does on that
+    track's file alone - into ``<out>/track<id>/``, one track after the other.  (Stepping the people of one camera as an
+    ``OnlineGroup`` is not done here: a group's sequences must all start at frame 0 and bring a detection to every step.)"""
+    from . import track as T
+    if not os.path.isdir(options.detections):
+        raise ValueError("--track 1 reads a directory of OpenPose *_keypoints.json files (--detections DIR): an .npz holds one person "
+                         "per frame already")
+    if adaptor is not None:
+        raise ValueError("--track 1 adapts every track from a fresh adaptation state: it builds its adaptors itself")
+    paths = T.track_openpose(options.detections, options.out, names, int(getattr(options, "min_track_frames", 1)),
+                             device="cuda" if device is None else device, **T.rule_of(options))
+    written = []
+    for t, path in paths.items():
+        ad = OnlineAdaptor(options, assets_bundle, device)
+        written += drive_frames(options, names, load_detections(path, names), ad, os.path.join(options.out, f"track{t}"))
+    return written
+
+
+def drive_frames(options, names: Sequence[str], dets: Dict[str, np.ndarray], ad: OnlineAdaptor, out: str) -> List[str]:
+    """The driver's loop: the frames `names` of ``--frames`` that have a detection through `ad` -> ``<out>/Pred_<n>...``."""
+    from PIL import Image
+    os.makedirs(out, exist_ok=True)
     # --overlay_format jpg: Pred_{n}.jpg from the device encoder; --overlay_video 1: Pred.avi beside the pictures (and, with
     # --one_euro 1, Pred_smooth.avi of the filtered mesh) - either makes the driver draw, as --save_video 1 does
     sink = sink_for(options, ad.device)
@@ -419,23 +454,23 @@ def run_driver(options, adaptor: Optional[OnlineAdaptor] = None, assets_bundle=N
             res = ad.online_adaptation(frame, dets[name])
             cam = res["cam"].detach()
             cam_t = torch.stack([cam[:, 1], cam[:, 2], 2 * C.FOCAL_LENGTH / (C.IMG_RES * cam[:, 0] + 1e-9)], dim=-1)
-            path = os.path.join(options.out, f"Pred_{n}.npz")
+            path = os.path.join(out, f"Pred_{n}.npz")
             np.savez(path, verts=res["vts"].detach().cpu().numpy(), cam=cam_t.cpu().numpy(), rotmat=res["rotmat"].cpu().numpy(),
                      beta=res["shape"].cpu().numpy())
             written.append(path)
             if sink is None:
                 if options.save_video:
-                    Image.fromarray(ad.render(res, frame).cpu().numpy()).save(os.path.join(options.out, f"Pred_{n}.png"))
+                    Image.fromarray(ad.render(res, frame).cpu().numpy()).save(os.path.join(out, f"Pred_{n}.png"))
                 continue
             pics, paths, videos = [], [], []
             if options.save_video or video:
                 pics.append(ad.render(res, frame))
-                paths.append(os.path.join(options.out, f"Pred_{n}.png") if options.save_video else None)
-                videos.append(os.path.join(options.out, "Pred.avi"))
+                paths.append(os.path.join(out, f"Pred_{n}.png") if options.save_video else None)
+                videos.append(os.path.join(out, "Pred.avi"))
             if video and "vts_smooth" in res:
                 pics.append(ad.render(res, frame, smooth=True))
                 paths.append(None)
-                videos.append(os.path.join(options.out, "Pred_smooth.avi"))
+                videos.append(os.path.join(out, "Pred_smooth.avi"))
             if pics:
                 sink.write(pics, paths, videos)
     finally:

@@ -444,6 +444,40 @@ int dyb_one_euro_step(float* state, const float* rotmat, const float* betas, int
                       const unsigned char* active, float te, float min_cutoff, float beta, float d_cutoff, float* rotmat_out,
                       float* betas_out, float* cam_out, int R, int J, dyb_stream_t stream);
 
+/* Person ids for detections that come without them (csrc/track.hip; the reference has no tracker and leaves association to external
+ * tools - the rule below is the definition, and tests/track_cases.py restates it in fp64 NumPy).  A batch of V videos: video v owns
+ * frames frame_offsets[v] .. frame_offsets[v + 1] of F, frame f owns detections det_offsets[f] .. det_offsets[f + 1] of n (both on the
+ * device, ascending, from 0; empty frames and empty videos are legal); kp [n][K][3] = (x, y, confidence) in pixels, 1 <= K <=
+ * DYB_TRACK_MAX_KP; frame_id [F] (NULL = the frame's position in its video), trusted to increase strictly within a video.
+ * A joint is VISIBLE iff its confidence is > c_min.  A detection with fewer than min_common visible joints is UNTRACKABLE: it gets
+ * track -1, matches nothing and starts nothing.  A detection's AREA is (max x - min x) * (max y - min y) over its visible joints.
+ * A video has at most DYB_TRACK_MAX_PEOPLE live tracks; a live track has an id, the keypoints, visibility and area of the last
+ * detection matched to it, and that detection's frame id `last`.  Per frame f, in this order:
+ *  1. retire: every track with frame_id[f] - last > max_age is retired;
+ *  2. score: for every live track t and trackable detection d among the frame's first DYB_TRACK_MAX_PEOPLE, with `common` the joints
+ *     visible in both: s = 0 if |common| < min_common, otherwise s = (sum over common, ascending k, of
+ *     expf(-(dx_k^2 + dy_k^2) / (2 kappa^2 A))) / |common| with A = max((area_t + area_d) / 2, 1), all in fp32;
+ *  3. greedy assignment: among the pairs with both sides free and s >= s_min take the largest s - ties go to the lower track id, then
+ *     to the lower detection index - assign it, and repeat until no pair is left;
+ *  4. update: a matched track takes the detection's keypoints, visibility, area and frame id whole;
+ *  5. new tracks: every unmatched trackable detection among the first DYB_TRACK_MAX_PEOPLE, in index order, starts a track with the
+ *     video's next id (ids count from 0 per video in order of creation) while fewer than DYB_TRACK_MAX_PEOPLE tracks are live;
+ *     otherwise it gets -1.  Detections past the DYB_TRACK_MAX_PEOPLE-th of a frame are not looked at and get -1.
+ * No constant-velocity prediction, no appearance term, no gap filling: a person lost for more than max_age frame ids comes back under
+ * a new id.  track_out [n]: the id or -1; sim_out [n] (may be NULL): the s a detection was matched with, 0 for one that started a
+ * track, -1 for one left without; video_out [V][DYB_TRACK_VIDEO_INTS]: tracks started, untrackable detections (among the frames' first
+ * DYB_TRACK_MAX_PEOPLE), detections left for lack of a slot (those past the DYB_TRACK_MAX_PEOPLE-th included), reserved 0.  One
+ * launch, one workgroup per video, nothing shared between them: two calls return equal bytes and a video's outputs do not depend on
+ * where it lies in the batch.  Stream ordered, no synchronisation.  DYB_ERR_ARG (nothing written): NULL kp or track_out with n > 0;
+ * NULL det_offsets, frame_offsets or video_out; K outside 1 .. DYB_TRACK_MAX_KP; kappa <= 0; s_min outside (0, 1]; max_age < 0;
+ * min_common < 1; a float that is not finite; n < 0, F < 0 or V < 1. */
+#define DYB_TRACK_MAX_PEOPLE 64
+#define DYB_TRACK_MAX_KP 32
+#define DYB_TRACK_VIDEO_INTS 4
+int dyb_track_videos(const float* kp, const int* det_offsets, const int* frame_offsets, const int* frame_id, int K, float c_min,
+                     float kappa, float s_min, int max_age, int min_common, int* track_out, float* sim_out, int* video_out, int n, int F,
+                     int V, dyb_stream_t stream);
+
 /* ---- flat-arena updates: learn2learn MAML.adapt (call sites dynaboa_benchmark.py:136,140),
  * torch.optim.Adam (base_adaptor.py:126; dynaboa_benchmark.py:149-151), update_teacher
  * (base_adaptor.py:193-201), cal_feature_diff's cosine (:211-219). n = float count, multiple of 4. */
